@@ -17,6 +17,13 @@ GPU -> VAE decode -> (N > 1) RCCL all-gather of final latents and decoded images
 Weights are seeded synthetic tensors of the exact SD1.5 / CLIP ViT-L/14 architecture and
 inputs are synthetic (no checkpoints or datasets exist offline).  Prints ONE JSON line.
 
+A plain run does only what the headline figure needs: set up, `--warmup` passes, `--steps` timed passes,
+the line (`value`, `ms_per_step`, ...).  `--full` adds everything else the benchmark measures or checks,
+after the timed passes: the clock / power sampler, the host margin, the roofline and best-kernel legs,
+parity against the CPU oracle and the CPU baseline.  `--dump-outputs DIR` writes what the last timed pass
+computed (the gathered final latents and decoded images, float32) as DIR/<name>.npy; inputs are seeded, so
+two builds can be compared output for output.
+
 Other BASELINE configs run through the same entry point (not the headline line):
     --guidance clustered_threshold          configs[2] guidance parameters (c3)
     --preset sd21 --size 768                configs[4] SD2.1-size UNet + OpenCLIP ViT-H guide (c5)
@@ -342,6 +349,24 @@ def devmon_collect(proc, t0: float, t1: float, device_bdf=None) -> dict:
     return out
 
 
+DUMP_LIMIT_BYTES = 60 << 20        # all dumped arrays together (64 MB minus room for the .npy headers)
+
+
+def dump_outputs(out_dir: str, arrays: dict, limit: int = DUMP_LIMIT_BYTES, seed: int = 0) -> None:
+    '''Writes every array as out_dir/<name>.npy in float32.  If together they exceed `limit` bytes, each one is replaced by a
+    fixed, seeded sample of its elements (flattened, in index order), sized to its share of the limit.'''
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.size * 4 for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > limit:
+            n = a.size * limit // total
+            idx = np.sort(np.random.default_rng(seed).choice(a.size, size=n, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
 def _free_port():
     with socket.socket() as s:
         s.bind(('127.0.0.1', 0))
@@ -452,8 +477,13 @@ def main():
     ap.add_argument('--size', type=int, default=512)
     ap.add_argument('--preset', default='sd15', choices=['sd15', 'sd21', 'mini', 'mini2'])
     ap.add_argument('--guidance', default='linear', choices=sorted(GUIDANCE))
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-parity', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed passes also measure and check everything beyond the headline figure: clock / power '
+                         'sampler, host margin, roofline and best-kernel legs, parity vs the CPU oracle, CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='write what the last timed pass computed (gathered latents and images, float32) as DIR/<name>.npy')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='(--full) skip the CPU baseline')
+    ap.add_argument('--no-parity', action='store_true', help='(--full) skip the parity legs')
     ap.add_argument('--graph', action='store_true', help='same as --launch graph')
     ap.add_argument('--launch', default='graph', choices=['graph', 'plan', 'eager'],
                     help='graph (default): the UNet forward is replayed from a captured HIP graph -- one host call per '
@@ -480,9 +510,9 @@ def main():
         plumbing_rank(args)
 
     # clock / power sampler: a child process (stdlib + amdsmi, never HIP), started before this process's
-    # first GPU call; rank 0's device only
+    # first GPU call; rank 0's device only; --full only
     devmon = None
-    if int(os.environ.get('RANK', '0')) == 0 and os.environ.get('FD_BENCH_DEVMON', '1') != '0':
+    if args.full and int(os.environ.get('RANK', '0')) == 0 and os.environ.get('FD_BENCH_DEVMON', '1') != '0':
         try:
             devmon = subprocess.Popen([sys.executable, os.path.join(ROOT, 'tools', 'devmon.py')],
                                       stdin=subprocess.PIPE, stdout=subprocess.PIPE, stderr=subprocess.DEVNULL,
@@ -586,101 +616,104 @@ def main():
     gc.collect()
     gc.freeze()
     sync()
+    last = None
     t0 = time.time()
     for k in range(args.steps):
-        one_pass()
+        last = one_pass()
     sync()
     t1 = time.time()
     elapsed = t1 - t0
-    try:
-        pr = torch.cuda.get_device_properties(torch.cuda.current_device())
-        timed_bdf = '%04x:%02x:%02x.0' % (getattr(pr, 'pci_domain_id', 0), pr.pci_bus_id, pr.pci_device_id)
-    except Exception:      # noqa: BLE001 -- older torch builds do not expose the PCI address
-        timed_bdf = None
-    device_state = devmon_collect(devmon, t0, t1, timed_bdf)
+    launch = 'graph' if pipe.use_graph else ('plan' if pipe.use_plan else 'eager')
     if dist.is_initialized():
         tmax = torch.tensor([elapsed], dtype=torch.float64,
                             device=dev if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
-
-    # ---- host margin: host time to ISSUE one CFG UNet forward vs device time to run it (the
-    # device is fed as long as the host is the faster of the two)
-    margin = None
-    if rank == 0:
-        sg = SimpleGuide(enc, pipe.unet, 8.0, args.ddim_steps,
-                         guide_ctx.embeds(prompt=prompts, guide=guide_img, **GUIDANCE[args.guidance]))
-        lat_m = pipe.loop_latents(noise)
-        ctx_m = sg.stacked_embeds()
-        for _ in range(2):
-            pipe._unet_eps(lat_m, 500, ctx_m, 2)
-        torch.cuda.synchronize()
-        n_m = 5
-        tm0 = time.time()
-        for i in range(n_m):
-            pipe._unet_eps(lat_m, 480 - 20 * i, ctx_m, 2)
-        tm1 = time.time()
-        torch.cuda.synchronize()
-        tm2 = time.time()
-        margin = {'host_ms_per_forward': 1e3 * (tm1 - tm0) / n_m,
-                  'device_ms_per_forward': 1e3 * (tm2 - tm0) / n_m,
-                  'launch': 'graph' if pipe.use_graph else ('plan' if pipe.use_plan else 'eager'),
-                  'launches_per_forward': pipe.plan_launches(),
-                  'note': 'issue time of 5 back-to-back CFG UNet forwards vs their completion time'}
-        margin['host_over_device'] = margin['host_ms_per_forward'] / margin['device_ms_per_forward']
-
-    # ---- roofline leg: one extra UNTIMED pass with a pair of HIP events on the launch stream around every launch of
-    # the library (the four families of FD_FAMILY_*).  Same launch mode as the timed region: where that replays a HIP
-    # graph the leg replays the recorded LAUNCH PLAN -- the same kernels, tiles and order issued by one host call per
-    # forward -- instead of the eager Python front (round 5's leg, whose host stalls ended up inside brackets).
-    # Aggregation: median per launch shape x count (aggregate_brackets).  If the families still do not fit in the step
-    # the leg is run once more (`roofline_retries`); `roofline_valid` says whether the final numbers fit.
-    fams, empty_ms, roofline_retries, roofline_valid = None, 0.0, 0, False
     ms_per_step = 1e3 * elapsed / args.steps
-    if rank == 0:
-        was_graph, was_plan = pipe.use_graph, pipe.use_plan
-        if pipe.use_graph:
-            pipe.use_graph, pipe.use_plan = False, True
-        one_pass()                        # records the plan (and warms the mode) with the recorder off
-        torch.cuda.synchronize()
-        for attempt in range(2 if world == 1 else 1):      # (N > 1: every rank takes part in each pass's all-gather -- no unilateral retry)
-            empty_ms = hip.prof_calibrate(256)
-            hip.prof_set_stride(EVENT_STRIDE)
-            hip.prof_enable(True)
-            one_pass(time_gather=(attempt == 0))
-            torch.cuda.synchronize()
-            hip.prof_enable(False)
-            fams = aggregate_brackets(*hip.prof_drain(), empty_ms, EVENT_STRIDE)
-            _, roofline_valid = time_budget(fams, ms_per_step)
-            roofline_retries = attempt
-            if roofline_valid:
-                break
-        pipe.use_graph, pipe.use_plan = was_graph, was_plan
-    elif dist.is_initialized():
-        one_pass()
-        one_pass(time_gather=True)       # every rank takes part in the extra passes' all-gathers
-        torch.cuda.synchronize()
+    if args.dump_outputs and rank == 0 and last is not None:
+        # what a caller of the timed path receives from its last pass: the gathered final latents and the decoded
+        # images (NHWC, as the pipeline's output_type='np' hands them out)
+        _, all_latents, all_images = last
+        dump_outputs(args.dump_outputs, {'latents': all_latents.float().cpu().numpy(),
+                                         'images': all_images.float().permute(0, 2, 3, 1).cpu().numpy()})
+    del last
 
-    import resource
-    rss_mib = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
-    rss_max = rss_mib
-    if dist.is_initialized():
-        t_rss = torch.tensor([rss_mib], dtype=torch.float64, device=dev if dist.get_backend() == 'nccl' else 'cpu')
-        dist.all_reduce(t_rss, op=dist.ReduceOp.MAX)
-        rss_max = float(t_rss[0])
+    # ---- everything beyond the headline figure runs with --full only, after the timed passes
+    if args.full:
+        try:
+            pr = torch.cuda.get_device_properties(torch.cuda.current_device())
+            timed_bdf = '%04x:%02x:%02x.0' % (getattr(pr, 'pci_domain_id', 0), pr.pci_bus_id, pr.pci_device_id)
+        except Exception:      # noqa: BLE001 -- older torch builds do not expose the PCI address
+            timed_bdf = None
+        device_state = devmon_collect(devmon, t0, t1, timed_bdf)
+
+        # ---- host margin: host time to ISSUE one CFG UNet forward vs device time to run it (the
+        # device is fed as long as the host is the faster of the two)
+        margin = None
+        if rank == 0:
+            sg = SimpleGuide(enc, pipe.unet, 8.0, args.ddim_steps,
+                             guide_ctx.embeds(prompt=prompts, guide=guide_img, **GUIDANCE[args.guidance]))
+            lat_m = pipe.loop_latents(noise)
+            ctx_m = sg.stacked_embeds()
+            for _ in range(2):
+                pipe._unet_eps(lat_m, 500, ctx_m, 2)
+            torch.cuda.synchronize()
+            n_m = 5
+            tm0 = time.time()
+            for i in range(n_m):
+                pipe._unet_eps(lat_m, 480 - 20 * i, ctx_m, 2)
+            tm1 = time.time()
+            torch.cuda.synchronize()
+            tm2 = time.time()
+            margin = {'host_ms_per_forward': 1e3 * (tm1 - tm0) / n_m,
+                      'device_ms_per_forward': 1e3 * (tm2 - tm0) / n_m,
+                      'launch': 'graph' if pipe.use_graph else ('plan' if pipe.use_plan else 'eager'),
+                      'launches_per_forward': pipe.plan_launches(),
+                      'note': 'issue time of 5 back-to-back CFG UNet forwards vs their completion time'}
+            margin['host_over_device'] = margin['host_ms_per_forward'] / margin['device_ms_per_forward']
+
+        # ---- roofline leg: one extra UNTIMED pass with a pair of HIP events on the launch stream around every launch of
+        # the library (the four families of FD_FAMILY_*).  Same launch mode as the timed region: where that replays a HIP
+        # graph the leg replays the recorded LAUNCH PLAN -- the same kernels, tiles and order issued by one host call per
+        # forward -- instead of the eager Python front (round 5's leg, whose host stalls ended up inside brackets).
+        # Aggregation: median per launch shape x count (aggregate_brackets).  If the families still do not fit in the step
+        # the leg is run once more (`roofline_retries`); `roofline_valid` says whether the final numbers fit.
+        fams, empty_ms, roofline_retries, roofline_valid = None, 0.0, 0, False
+        if rank == 0:
+            was_graph, was_plan = pipe.use_graph, pipe.use_plan
+            if pipe.use_graph:
+                pipe.use_graph, pipe.use_plan = False, True
+            one_pass()                        # records the plan (and warms the mode) with the recorder off
+            torch.cuda.synchronize()
+            for attempt in range(2 if world == 1 else 1):      # (N > 1: every rank takes part in each pass's all-gather -- no unilateral retry)
+                empty_ms = hip.prof_calibrate(256)
+                hip.prof_set_stride(EVENT_STRIDE)
+                hip.prof_enable(True)
+                one_pass(time_gather=(attempt == 0))
+                torch.cuda.synchronize()
+                hip.prof_enable(False)
+                fams = aggregate_brackets(*hip.prof_drain(), empty_ms, EVENT_STRIDE)
+                _, roofline_valid = time_budget(fams, ms_per_step)
+                roofline_retries = attempt
+                if roofline_valid:
+                    break
+            pipe.use_graph, pipe.use_plan = was_graph, was_plan
+        elif dist.is_initialized():
+            one_pass()
+            one_pass(time_gather=True)       # every rank takes part in the extra passes' all-gathers
+            torch.cuda.synchronize()
+
+        import resource
+        rss_mib = resource.getrusage(resource.RUSAGE_SELF).ru_maxrss / 1024.0
+        rss_max = rss_mib
+        if dist.is_initialized():
+            t_rss = torch.tensor([rss_mib], dtype=torch.float64, device=dev if dist.get_backend() == 'nccl' else 'cpu')
+            dist.all_reduce(t_rss, op=dist.ReduceOp.MAX)
+            rss_max = float(t_rss[0])
+
     if rank == 0:
         images = B * N * args.steps
         value = images / elapsed
-        g, att, gn = fams['gemm'], fams['attention'], fams['groupnorm']
-        achieved = (g['work'] / (g['ms'] * 1e-3)) / 1e12 if g['ms'] > 0 else 0.0
-        executed = (g['executed'] / (g['ms'] * 1e-3)) / 1e12 if g['ms'] > 0 else 0.0
-        budget, _ = time_budget(fams, ms_per_step)
-        fam_sum = g['ms'] + att['ms'] + gn['ms']
-        # HBM bytes of the dominant kernel (level-0 conv3x3) from its PMC pass: rocprofv3 cannot
-        # run inside this process, so the committed per-launch measurement is reported with its
-        # source (it is NOT re-measured by this run)
-        traffic, traffic_of, traffic_other, traffic_stale = pick_traffic_record()
-        fpi = flops_per_image(args.preset, hw, ddim_evals)
         headline = (args.preset == 'sd15' and hw == 512 and args.ddim_steps == 50 and args.scheduler == 'ddim'
                     and args.guidance == 'linear' and B == 8 and not args.img2img)
         cfg_name = {('sd15', 'linear', False): 'BASELINE configs[1]',
@@ -703,68 +736,82 @@ def main():
                                    f'guidance, CFG 8, batch={B}/GPU ({cfg_name})',
                        'images_per_step': B * N, 'parallelism': f'seed-sharded x{N}',
                        'preset': args.preset, 'guidance': args.guidance, 'img2img': args.img2img,
-                       'unet_evaluations_per_image': ddim_evals, 'launch': margin['launch'],
+                       'unet_evaluations_per_image': ddim_evals, 'launch': launch,
                        'scheduler': args.scheduler, 'launch_note': launch_note},
             # ranks that took part in an RCCL (torch.distributed "nccl") process group; 0 for any
             # other backend (gloo plumbing runs) and for an undistributed N=1 run
             'rccl_ranks': dist.get_world_size() if dist.is_initialized() and dist.get_backend() == 'nccl' else 0,
             'dist_backend': dist.get_backend() if dist.is_initialized() else None,
-            'host_margin': margin, 'host_ms_per_forward': margin['host_ms_per_forward'],
-            'all_gather': {'bytes_per_rank': gather['bytes_per_rank'],
-                           'ms': gather['ms'] / max(gather['calls'], 1),
-                           'backend': ('RCCL (torch.distributed nccl)' if dist.get_backend() == 'nccl'
-                                       else dist.get_backend()) if dist.is_initialized() else 'none (N=1)'},
-            'roofline': {
-                'bound': 'mfma', 'kernel': 'k_gemm_f16 (implicit-GEMM conv3x3 / GEMM family)',
-                'achieved': achieved, 'peak': MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                'frac': achieved / MFMA_PEAK_TFLOPS,
-                # MACs the kernels really issued / time / peak: `achieved` prices every launch at the ALGORITHMIC work of
-                # the op it implements (a parity-decomposed upsample convolution executes 4/9 of its 3x3 MACs, a Winograd
-                # F(2x2,3x3) convolution 4/9 as well); this is the hardware-side rate of the same launches
-                'executed': executed, 'executed_frac': executed / MFMA_PEAK_TFLOPS,
-                'traffic': traffic, 'traffic_of': traffic_of,
-                # false only when the PMC record was collected on exactly these GEMM sources (sha256 recorded with it)
-                'traffic_stale': traffic_stale,
-                'traffic_other_kernels': traffic_other,
-                # one untimed pass in the timed region's launch mode (graph -> the recorded launch plan), every launch
-                # bracketed by HIP events on its stream; per launch shape MEDIAN bracket - empty bracket, x launch count
-                'leg_launch': 'plan' if margin['launch'] == 'graph' else margin['launch'],
-                'aggregation': 'median per (family, launch shape) x launches',
-                'sampled_every': EVENT_STRIDE, 'sampled_launches': g['launches'] // EVENT_STRIDE,
-                'launches': g['launches'], 'launch_shapes': g['groups'],
-                'empty_bracket_us': 1e3 * empty_ms,
-                'kernel_ms_per_pass': g['ms'], 'kernel_ms_per_pass_plain_sum': g['raw_ms'] - g['launches'] * empty_ms,
-                'avg_launch_us': 1e3 * g['ms'] / g['launches'] if g['launches'] else None,
-                'attention_tflops': (att['work'] / (att['ms'] * 1e-3)) / 1e12 if att['ms'] else 0.0,
-                'attention_ms_per_pass': att['ms'],
-                # GroupNorm priced at SURVEY 8(d)'s 4 B/element (fp16 read + write)
-                'groupnorm_gbps': (gn['work'] / (gn['ms'] * 1e-3)) / 1e9 if gn['ms'] else 0.0,
-                'groupnorm_frac_of_hbm': ((gn['work'] / (gn['ms'] * 1e-3)) / 1e9 / HBM_PEAK_GBPS) if gn['ms'] else 0.0,
-                'groupnorm_ms_per_pass': gn['ms'],
-                'other_kernels_ms_per_pass': fams['other_kernels']['ms'],
-                'families_ms_per_pass': fam_sum,
-                'families_fit_in_step': fam_sum <= ms_per_step,
-                # sums to ms_per_step: the four families of library launches + everything else (device-side launch gaps,
-                # torch's fill / copy kernels, the device->host copy of the images, host work the device waits for)
-                'time_budget_ms': budget,
-                'roofline_valid': roofline_valid, 'roofline_retries': roofline_retries,
-                'worst_bracket_over_median': {k: v['worst_bracket_over_median'] for k, v in fams.items()},
-                'end_to_end_frac_of_mfma_roofline':
-                    (value / N) * fpi / (MFMA_PEAK_TFLOPS * 1e12) if fpi else None,
-            },
-            'device': dict(info, **device_state), 'setup_s': t_setup,
-            # peak resident set of a rank's host process (MiB): rank 0's, and the largest over the ranks
-            'host_rss_mib': {'rank0': rss_mib, 'max_over_ranks': rss_max},
+            'device': dict(info), 'setup_s': t_setup,
         }
-        line['roofline']['best_kernel'] = best_kernel_leg(dev)
-        line['roofline']['frac_best_kernel'] = line['roofline']['best_kernel']['frac']
-        if N == 1 and not args.no_parity and args.preset == 'sd15':
-            line['parity'] = {'c1': parity_c1(sds, cfgs, pipe, enc, tok)}
-            c2 = parity_c2(sds, cfgs, pipe, guide_ctx, enc)
-            if c2 is not None:
-                line['parity']['c2'] = c2
-        if N == 1 and not args.no_cpu_baseline:
-            line['cpu_baseline'] = cpu_baseline(sds, cfgs, args.ddim_steps, hw)
+        if args.full:
+            g, att, gn = fams['gemm'], fams['attention'], fams['groupnorm']
+            achieved = (g['work'] / (g['ms'] * 1e-3)) / 1e12 if g['ms'] > 0 else 0.0
+            executed = (g['executed'] / (g['ms'] * 1e-3)) / 1e12 if g['ms'] > 0 else 0.0
+            budget, _ = time_budget(fams, ms_per_step)
+            fam_sum = g['ms'] + att['ms'] + gn['ms']
+            # HBM bytes of the dominant kernel (level-0 conv3x3) from its PMC pass: rocprofv3 cannot
+            # run inside this process, so the committed per-launch measurement is reported with its
+            # source (it is NOT re-measured by this run)
+            traffic, traffic_of, traffic_other, traffic_stale = pick_traffic_record()
+            fpi = flops_per_image(args.preset, hw, ddim_evals)
+            line.update({
+                'host_margin': margin, 'host_ms_per_forward': margin['host_ms_per_forward'],
+                'all_gather': {'bytes_per_rank': gather['bytes_per_rank'],
+                               'ms': gather['ms'] / max(gather['calls'], 1),
+                               'backend': ('RCCL (torch.distributed nccl)' if dist.get_backend() == 'nccl'
+                                           else dist.get_backend()) if dist.is_initialized() else 'none (N=1)'},
+                'roofline': {
+                    'bound': 'mfma', 'kernel': 'k_gemm_f16 (implicit-GEMM conv3x3 / GEMM family)',
+                    'achieved': achieved, 'peak': MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                    'frac': achieved / MFMA_PEAK_TFLOPS,
+                    # MACs the kernels really issued / time / peak: `achieved` prices every launch at the ALGORITHMIC work of
+                    # the op it implements (a parity-decomposed upsample convolution executes 4/9 of its 3x3 MACs, a Winograd
+                    # F(2x2,3x3) convolution 4/9 as well); this is the hardware-side rate of the same launches
+                    'executed': executed, 'executed_frac': executed / MFMA_PEAK_TFLOPS,
+                    'traffic': traffic, 'traffic_of': traffic_of,
+                    # false only when the PMC record was collected on exactly these GEMM sources (sha256 recorded with it)
+                    'traffic_stale': traffic_stale,
+                    'traffic_other_kernels': traffic_other,
+                    # one untimed pass in the timed region's launch mode (graph -> the recorded launch plan), every launch
+                    # bracketed by HIP events on its stream; per launch shape MEDIAN bracket - empty bracket, x launch count
+                    'leg_launch': 'plan' if launch == 'graph' else launch,
+                    'aggregation': 'median per (family, launch shape) x launches',
+                    'sampled_every': EVENT_STRIDE, 'sampled_launches': g['launches'] // EVENT_STRIDE,
+                    'launches': g['launches'], 'launch_shapes': g['groups'],
+                    'empty_bracket_us': 1e3 * empty_ms,
+                    'kernel_ms_per_pass': g['ms'], 'kernel_ms_per_pass_plain_sum': g['raw_ms'] - g['launches'] * empty_ms,
+                    'avg_launch_us': 1e3 * g['ms'] / g['launches'] if g['launches'] else None,
+                    'attention_tflops': (att['work'] / (att['ms'] * 1e-3)) / 1e12 if att['ms'] else 0.0,
+                    'attention_ms_per_pass': att['ms'],
+                    # GroupNorm priced at SURVEY 8(d)'s 4 B/element (fp16 read + write)
+                    'groupnorm_gbps': (gn['work'] / (gn['ms'] * 1e-3)) / 1e9 if gn['ms'] else 0.0,
+                    'groupnorm_frac_of_hbm': ((gn['work'] / (gn['ms'] * 1e-3)) / 1e9 / HBM_PEAK_GBPS) if gn['ms'] else 0.0,
+                    'groupnorm_ms_per_pass': gn['ms'],
+                    'other_kernels_ms_per_pass': fams['other_kernels']['ms'],
+                    'families_ms_per_pass': fam_sum,
+                    'families_fit_in_step': fam_sum <= ms_per_step,
+                    # sums to ms_per_step: the four families of library launches + everything else (device-side launch gaps,
+                    # torch's fill / copy kernels, the device->host copy of the images, host work the device waits for)
+                    'time_budget_ms': budget,
+                    'roofline_valid': roofline_valid, 'roofline_retries': roofline_retries,
+                    'worst_bracket_over_median': {k: v['worst_bracket_over_median'] for k, v in fams.items()},
+                    'end_to_end_frac_of_mfma_roofline':
+                        (value / N) * fpi / (MFMA_PEAK_TFLOPS * 1e12) if fpi else None,
+                },
+                'device': dict(info, **device_state),
+                # peak resident set of a rank's host process (MiB): rank 0's, and the largest over the ranks
+                'host_rss_mib': {'rank0': rss_mib, 'max_over_ranks': rss_max},
+            })
+            line['roofline']['best_kernel'] = best_kernel_leg(dev)
+            line['roofline']['frac_best_kernel'] = line['roofline']['best_kernel']['frac']
+            if N == 1 and not args.no_parity and args.preset == 'sd15':
+                line['parity'] = {'c1': parity_c1(sds, cfgs, pipe, enc, tok)}
+                c2 = parity_c2(sds, cfgs, pipe, guide_ctx, enc)
+                if c2 is not None:
+                    line['parity']['c2'] = c2
+            if N == 1 and not args.no_cpu_baseline:
+                line['cpu_baseline'] = cpu_baseline(sds, cfgs, args.ddim_steps, hw)
         print(json.dumps(line), flush=True)
     if dist.is_initialized():
         dist.barrier()

@@ -79,10 +79,40 @@ def test_bench_defaults_finish_in_minutes_and_help_parses():
     r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, timeout=120)
     assert r.returncode == 0
     text = r.stdout.decode()
-    for flag in ('--gpus', '--steps', '--warmup', '--launch', '--scheduler', '--img2img', '--guidance', '--preset'):
+    for flag in ('--gpus', '--steps', '--warmup', '--launch', '--scheduler', '--img2img', '--guidance', '--preset', '--full',
+                 '--dump-outputs'):
         assert flag in text, flag
     # importing bench must not import torch (the N-rank parent stays GPU-free); defaults: N = 1, 8 timed / 2 warm-up passes
     code = ('import sys; sys.argv = ["bench.py"]; sys.path.insert(0, %r); import bench, argparse; '
             'assert "torch" not in sys.modules; print("ok")' % ROOT)
     r = subprocess.run([sys.executable, '-c', code], capture_output=True, timeout=120)
     assert r.returncode == 0 and b'ok' in r.stdout, r.stderr.decode()[-500:]
+
+
+def test_dump_outputs_stays_within_its_size_limit():
+    '''bench.dump_outputs: float32 .npy per array; above the limit every array becomes a fixed, seeded sample of its elements.'''
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    argv, sys.argv = sys.argv, ['bench.py']
+    try:
+        import bench
+    finally:
+        sys.argv = argv
+    import tempfile
+    rng = np.random.default_rng(0)
+    arrays = {'latents': rng.standard_normal((4, 4, 8, 8)), 'images': rng.random((4, 64, 64, 3))}
+    with tempfile.TemporaryDirectory() as d:
+        bench.dump_outputs(d, arrays)
+        for name, a in arrays.items():
+            got = np.load(os.path.join(d, name + '.npy'))
+            assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32))
+        limit = 16 << 10
+        bench.dump_outputs(os.path.join(d, 's1'), arrays, limit=limit)
+        bench.dump_outputs(os.path.join(d, 's2'), arrays, limit=limit)
+        total = 0
+        for name, a in arrays.items():
+            s1, s2 = (np.load(os.path.join(d, s, name + '.npy')) for s in ('s1', 's2'))
+            assert s1.dtype == np.float32 and s1.ndim == 1 and np.array_equal(s1, s2)
+            assert np.isin(s1, a.astype(np.float32).reshape(-1)).all()
+            total += s1.nbytes
+        assert 0.9 * limit < total <= limit

@@ -61,8 +61,9 @@ def _bench(args, **env):
     return json.loads(lines[0])
 
 
+# --full: the tests below read the host margin, the all-gather and roofline objects, which only a --full run measures
 MINI = ['--preset', 'mini', '--size', '64', '--ddim-steps', '3', '--batch', '2', '--steps', '1',
-        '--warmup', '1', '--no-cpu-baseline', '--no-parity']
+        '--warmup', '1', '--no-cpu-baseline', '--no-parity', '--full']
 
 
 def test_bench_launches_two_ranks():
@@ -117,3 +118,26 @@ def test_bench_single_rank_rccl_line():
     rf = line['roofline']
     assert rf['bound'] == 'mfma' and rf['peak'] == 2516.6 and 0 < rf['frac'] < 1
     assert rf['families_fit_in_step'] and 0 < rf['frac_best_kernel'] < 1
+
+
+def test_plain_mini_bench_line_and_dumped_outputs(tmp_path):
+    '''A plain run (no --full) prints the headline fields only, times exactly --steps passes, and --dump-outputs writes the
+    last timed pass's gathered latents and images as float32 .npy files -- the same arrays on a second run with the same
+    arguments (seeded inputs).'''
+    import numpy as np
+    plain = [a for a in MINI if a != '--full']
+    plain[plain.index('--steps') + 1] = '2'
+    dumps = []
+    for run in ('a', 'b'):
+        line = _bench(plain + ['--dump-outputs', str(tmp_path / run)])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in line, k
+        assert line['steps'] == 2 and line['unit'] == 'images/sec' and line['dtype'] == 'fp16'
+        assert abs(line['value'] - line['config']['images_per_step'] * 1e3 / line['ms_per_step']) < 1e-6 * line['value']
+        assert not {'roofline', 'host_margin', 'all_gather', 'parity', 'cpu_baseline'} & set(line)
+        lat, img = np.load(tmp_path / run / 'latents.npy'), np.load(tmp_path / run / 'images.npy')
+        assert lat.dtype == np.float32 and lat.shape == (2, 4, 8, 8) and np.isfinite(lat).all()
+        assert img.dtype == np.float32 and img.ndim == 4 and img.shape[0] == 2 and img.shape[-1] == 3
+        assert 0 <= img.min() and img.max() <= 1
+        dumps.append((lat, img))
+    assert np.array_equal(dumps[0][0], dumps[1][0]) and np.array_equal(dumps[0][1], dumps[1][1])
