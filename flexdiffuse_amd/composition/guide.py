@@ -4,16 +4,22 @@ batch over [uncond, background, entity_1..n] on the same latents, each entity's 
 prediction blended onto the background inside its latent-space rectangle
 (bg + blend * (entity - bg)), then classifier-free guidance against the unconditional row.
 
-Like the reference it is defined for batch_size == 1 (the reference concatenates
-`latents` once per embedding row).  The style-blend embedding the reference computes at
-composition/guide.py:114-121 is dead code there and is not evaluated here.
+The reference runs only batch_size == 1 (it concatenates `latents` once per embedding row).
+Beyond it: `batch_size = B > 1` (B independent compositions in ONE UNet forward over E*B rows,
+context in rep-major order [uncond]*B [bg]*B [e_1]*B ...) and soft entity masks (weight
+blend * mean of the mask's 8x8 pixel cell per latent cell).  Those requests blend, combine and (in
+FlexPipeline's device loop) take the DDIM step in one launch, fd_composite_step_f32; batch 1 without
+masks keeps the per-entity fd_region_blend_f32 chain.  The style-blend embedding the reference
+computes at composition/guide.py:114-121 is dead code there and is not evaluated here.
 '''
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import List, Sequence, Tuple
+from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
+import torch.nn.functional as F
 
 from .. import hip, ops
 from ..pipeline.guide import GuideBase
@@ -30,40 +36,98 @@ class EntityEmbeds():
     offset_blocks: Tuple[int, int]
     size_blocks: Tuple[int, int]
     blend: float
+    mask: Optional[np.ndarray] = None
+
+
+def box_slices(offset_blocks: Sequence[int], size_blocks: Sequence[int], H: int, W: int) -> Tuple[int, int, int, int]:
+    '''(y0, y1, x0, x1) of an entity's latent box.  composition/guide.py:86-98 slices
+    noise[:, :, oh:oh+sh, ow:ow+sw]: Python slice semantics -- a box past the canvas is clipped, a
+    NEGATIVE start counts from the end of the axis (usually leaving an empty box, i.e. no blend at all).'''
+    (ow, oh), (sw, sh) = offset_blocks, size_blocks
+    y0, y1, _ = slice(oh, oh + sh).indices(H)
+    x0, x1, _ = slice(ow, ow + sw).indices(W)
+    return y0, y1, x0, x1
+
+
+def weight_maps(entities: Sequence[EntityEmbeds], H: int, W: int) -> torch.Tensor:
+    '''Dense fp32 [n][H][W] blend weights (CPU), 0 outside every box: fp32(blend) inside a rectangle;
+    fp32(blend) * fp32(cell) with a mask, `cell` the mean of the mask's 8x8 image-pixel block (floor, as
+    px_to_block).  The mask's top-left cell sits at the box's resolved origin; cells past the canvas are dropped.'''
+    out = torch.zeros((len(entities), H, W), dtype=torch.float32)
+    for k, e in enumerate(entities):
+        y0, y1, x0, x1 = box_slices(e.offset_blocks, e.size_blocks, H, W)
+        if y1 <= y0 or x1 <= x0:
+            continue
+        blend = torch.tensor(float(e.blend), dtype=torch.float32)
+        if e.mask is None:
+            out[k, y0:y1, x0:x1] = blend
+        else:
+            cell = F.avg_pool2d(torch.from_numpy(e.mask)[None, None], 8)[0, 0]
+            out[k, y0:y1, x0:x1] = blend * cell[:y1 - y0, :x1 - x0]
+    return out
 
 
 class CompositeGuide(GuideBase):
     def __init__(self, encoder, unet, guidance: float, schema: Schema, steps: int,
                  batch_size: int = 1):
         GuideBase.__init__(self, encoder, unet, guidance, steps)
-        if batch_size != 1:
-            raise ValueError('CompositeGuide is defined for batch_size == 1 (as in the reference)')
+        if int(batch_size) < 1:
+            raise ValueError(f'batch_size must be >= 1, got {batch_size}')
         self.schema = schema
         self.background_embed = encoder.prompt(schema.background_prompt)
         self.entities: List[EntityEmbeds] = [
             EntityEmbeds(encoder.prompt(e.prompt), px_to_block(e.offset), px_to_block(e.size),
-                         e.blend) for e in schema.entities]
-        self.batch_size = batch_size
+                         e.blend, getattr(e, 'mask', None)) for e in schema.entities]
+        self.batch_size = B = int(batch_size)
         self.classifier_free_guidance = self.guidance > 1.0
+        # batched or masked requests: one fd_composite_step_f32 per step, on FlexPipeline's device loop
+        self.on_device = B > 1 or any(e.mask is not None for e in self.entities)
         rows = [self.background_embed] + [e.embed for e in self.entities]
         if self.classifier_free_guidance:
-            rows = [self.uncond_embeds] * self.batch_size + rows
-        self.embed_tensor = torch.cat([r.float() for r in rows]).contiguous()
+            rows = [self.uncond_embeds] + rows
+        self.rep = len(rows)                     # E: context blocks of B rows each
+        # built once, rep-major: [uncond]*B, [bg]*B, [e_1]*B ... -- for B = 1 the reference's [uncond, bg, e_1, ...]
+        self.embed_tensor = torch.cat([r.float().expand(B, -1, -1) for r in rows]).contiguous()
+        self._wmaps = {}
+
+    def stacked_embeds(self) -> torch.Tensor:
+        return self.embed_tensor
+
+    def weights(self, H: int, W: int) -> Optional[torch.Tensor]:
+        '''Device fp32 [n][H][W] blend weights (None without entities), built once per latent size and kept: a
+        captured graph / recorded plan of the step reads this buffer.'''
+        if not self.entities:
+            return None
+        w = self._wmaps.get((H, W))
+        if w is None:
+            w = weight_maps(self.entities, H, W).to(self.embed_tensor.device)
+            self._wmaps[(H, W)] = w
+        return w
+
+    def step(self, x: Optional[torch.Tensor], eps: torch.Tensor, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
+             eps_out: Optional[torch.Tensor] = None):
+        '''Blend + CFG of the UNet output `eps` (NHWC fp32, rep-major rows) into `eps_out` (NCHW fp32, optional) and,
+        given `x` (NCHW fp32), the DDIM update of `x` in place: one launch.'''
+        B, C, H, W = (x if x is not None else eps_out).shape
+        ops.composite_step(x, eps, self.weights(H, W), B, C, H * W, self.classifier_free_guidance, self.guidance,
+                           coef, v_prediction, do_step=x is not None, eps_out=eps_out)
 
     def noise_pred(self, latents: torch.Tensor, step) -> torch.Tensor:
-        E = self.embed_tensor.shape[0]
-        _, C, H, W = latents.shape
+        E = self.rep
+        B, C, H, W = latents.shape
+        if self.on_device:
+            if B != self.batch_size:
+                raise ValueError(f'latents batch {B} != the guide\'s batch_size {self.batch_size}')
+            eps = self.unet.forward_nhwc(latents, step, self.embed_tensor, rep=E)
+            out = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
+            self.step(None, eps, eps_out=out)
+            return out
         eps = self.unet.forward_nhwc(latents, step, self.embed_tensor, rep=E)
         stack = ops.nhwc_to_nchw(eps, E, C, H, W)            # (E,C,H,W) fp32
         first = 1 if self.classifier_free_guidance else 0
         bg = stack[first]
         for k, e in enumerate(self.entities):
-            (ow, oh), (sw, sh) = e.offset_blocks, e.size_blocks
-            # composition/guide.py:86-98 slices noise[:, :, oh:oh+sh, ow:ow+sw]: Python slice
-            # semantics -- a box past the canvas is clipped, a NEGATIVE start counts from the end
-            # of the axis (usually leaving an empty box, i.e. no blend at all)
-            y0, y1, _ = slice(oh, oh + sh).indices(H)
-            x0, x1, _ = slice(ow, ow + sw).indices(W)
+            y0, y1, x0, x1 = box_slices(e.offset_blocks, e.size_blocks, H, W)
             if y1 <= y0 or x1 <= x0:
                 continue
             hip.call('fd_region_blend_f32', bg.data_ptr(), stack[first + 1 + k].data_ptr(), C, H, W,

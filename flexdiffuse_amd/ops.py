@@ -905,6 +905,24 @@ def cfg_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: 
              float(coef[2]), float(coef[3]), int(v_prediction), int(do_step), hip.stream())
 
 
+def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
+                   HW: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
+                   do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
+    '''CompositeGuide step (fd_composite_step_f32): eps_nhwc [(cfg + 1 + n) * B * HW][ld] fp32 in rep-major order,
+    weights [n][HW] fp32 (None: no entity) -> blend, CFG, optionally the DDIM update of x (NCHW fp32, in place).'''
+    n = 0 if weights is None else weights.shape[0]
+    rows = ((1 if cfg else 0) + 1 + n) * B * HW
+    assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
+    assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
+    if weights is not None:
+        assert weights.dtype == torch.float32 and weights.is_contiguous() and weights[0].numel() == HW
+    for t in (x, eps_out):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW)
+    hip.call('fd_composite_step_f32', _p(x), eps_nhwc.data_ptr(), _p(weights), _p(eps_out), B, C, HW,
+             eps_nhwc.stride(0), n, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
+             float(coef[3]), int(v_prediction), int(do_step), hip.stream())
+
+
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
           exp_half_x: bool = False) -> torch.Tensor:
     x = x.contiguous()

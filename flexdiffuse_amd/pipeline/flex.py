@@ -3,7 +3,8 @@
 _latents_to_image :112-124, __call__ :126-310) with the same call signature, return types
 and ValueError, driving the gfx950 kernels.
 
-Device loop: for `SimpleGuide` + DDIM the whole step is  UNet(NHWC fp16, CFG batch built
+Device loop: for `SimpleGuide` (and a batched or masked `CompositeGuide`, whose blend + CFG + DDIM
+update is one fd_composite_step_f32) + DDIM the whole step is  UNet(NHWC fp16, CFG batch built
 inside the layout kernel) -> fused CFG + DDIM update on the fp32 latents  with no host
 round trip; any other guide object goes through the reference protocol
 (`guide.noise_pred` + `scheduler.step`) unchanged.  The UNet forward of the fused loop is
@@ -333,13 +334,19 @@ class FlexPipeline():
 
         latents = init_latents.contiguous()
         all_latents = [init_latents] if debug else None
-        fused = (type(guide).noise_pred is SimpleGuide.noise_pred
+        from ..composition.guide import CompositeGuide
+        # CompositeGuide with batched samples or masks: blend + CFG (+ DDIM update) in one launch per step after the
+        # UNet forward over its E context blocks (the batch-1 rectangle path stays on the generic protocol)
+        comp = (type(guide).noise_pred is CompositeGuide.noise_pred and getattr(guide, 'on_device', False)
+                and hasattr(self.unet, 'forward_nhwc'))
+        device_guide = type(guide).noise_pred is SimpleGuide.noise_pred or comp
+        fused = (device_guide
                  and isinstance(self.scheduler, DDIMScheduler) and not eta
                  and hasattr(self.unet, 'forward_nhwc'))
         B, C, H, W = latents.shape
         # SimpleGuide with ANY other scheduler (PNDM -- what the reference's Runner passes, utils.py:70 -- LMS, DDIM with
         # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
-        planned = (not fused and type(guide).noise_pred is SimpleGuide.noise_pred and hasattr(self.unet, 'forward_nhwc')
+        planned = (not fused and device_guide and hasattr(self.unet, 'forward_nhwc')
                    and (self.use_graph or self.use_plan) and not debug)
         if fused and (self.use_graph or self.use_plan) and not debug:
             # persistent latent buffer: the captured UNet graph / recorded plan reads this address
@@ -361,16 +368,22 @@ class FlexPipeline():
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps[t_start:])):
                 if fused:
                     cfg = guide.classifier_free_guidance
+                    rep = guide.rep if comp else 2 if cfg else 1
                     if debug:
+                        # (a composite reads the request's time-bias table as the graph / plan do: bit-equal to them)
+                        temb = self._temb_row(int(t)).expand(B * rep, -1).contiguous() if comp and self._temb_tab else None
                         eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(),
-                                                     rep=2 if cfg else 1)
+                                                     rep=rep, temb=temb)
                     else:
-                        eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), 2 if cfg else 1)
+                        eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
                     coef = self.scheduler.step_coefficients(int(t))[:4]
                     if debug:
                         latents = latents.clone()
-                    ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef,
-                                      self.scheduler.config['prediction_type'] == 'v_prediction')
+                    vpred = self.scheduler.config['prediction_type'] == 'v_prediction'
+                    if comp:
+                        guide.step(latents, eps, coef, vpred)
+                    else:
+                        ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
                 else:
                     t_index, model_input = t, latents
                     if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling
@@ -380,9 +393,12 @@ class FlexPipeline():
                     if planned:
                         cfg = guide.classifier_free_guidance
                         eps = self._unet_eps(self.loop_latents(model_input), float(t), guide.stacked_embeds(),
-                                             2 if cfg else 1)
+                                             guide.rep if comp else 2 if cfg else 1)
                         noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
-                        ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
+                        if comp:
+                            guide.step(None, eps, eps_out=noise_pred)
+                        else:
+                            ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
                     else:
                         noise_pred = guide.noise_pred(model_input, t)
                     latents = self.scheduler.step(noise_pred, t_index, latents,

@@ -14,6 +14,7 @@ of GPUs; no CUDA autocast context is needed (the kernels are fp16 MFMA by constr
 '''
 from __future__ import annotations
 
+import dataclasses
 import gc
 import math
 import os
@@ -163,13 +164,26 @@ class Runner():
                 guidance_scale: float = 8.0,
                 init_size: Tuple[int, int] = (512, 512),
                 seed: Optional[int] = None,
-                debug: bool = False):
+                debug: bool = False,
+                *,
+                batch_size: int = 1,
+                masks: Optional[Sequence[Any]] = None):
         '''Same arguments and defaults as utils.py:168-181; returns (images, grid).  `entities_df`
         rows are [prompt, offset_x, offset_y, width, height, blend]; a DataFrame is taken through
-        its `_values` (utils.py:198-199); rows that do not parse or have an empty prompt are dropped.'''
+        its `_values` (utils.py:198-199); rows that do not parse or have an empty prompt are dropped.
+        Beyond the reference: `batch_size` samples per pipeline call (one UNet forward; `batches *
+        batch_size` images in all) and `masks`, aligned with the table rows (None: the rectangle),
+        each an EntitySchema mask over its box.'''
         self._set_seed(seed)
         table = getattr(entities_df, '_values', entities_df)
-        entities = [e for e in map(entity_from_row, table) if e is not None and e.prompt]
+        parsed = [entity_from_row(row) for row in table]
+        if masks is not None:
+            if len(masks) != len(parsed):
+                raise ValueError(f'{len(masks)} masks for {len(parsed)} table rows')
+            # attached before rows are dropped, so the alignment with the table holds
+            parsed = [e if e is None or m is None else dataclasses.replace(e, mask=m) for e, m in zip(parsed, masks)]
+        entities = [e for e in parsed if e is not None and e.prompt]
         self.last_schema = Schema(bg_prompt, start_style, end_style, style_blend, entities)
-        guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps)
+        extra = {'batch_size': batch_size} if batch_size != 1 else {}
+        guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps, **extra)
         return self._run(batches, guide, init_image, init_size, strength, debug)

@@ -451,6 +451,16 @@ int fd_repeat_rows_f16(const void* src, int lds, void* dst, int ldd, int64_t row
  * the box is clipped to the canvas. */
 int fd_region_blend_f32(float* dst, const float* src, int C, int H, int W, int oy, int ox, int sh,
                         int sw, float blend, void* stream);
+/* CompositeGuide on the device loop, one launch per step: the region blend of composition/guide.py:86-98
+ * with a per-cell weight, the CFG combine of pipeline/guide.py:59-63 and, with do_step, the DDIM update of
+ * fd_cfg_ddim_step_f32 (same coefficients, eps- or v-prediction).  eps_nhwc: UNet output, E = cfg + 1 + n
+ * blocks of B samples in rep-major order ([uncond] [background] [entity 0] ... [entity n-1]); row
+ * (r * B + b) * HW + p, row stride ld.  weights: fp32 [n][HW] (shared by the B samples), 0 outside an
+ * entity's box.  Per (b, c, p): v = bg; for each k with w_k(p) != 0: v += w_k(p) * (ent_k - v); with cfg
+ * v = u + g (v - u).  eps_out (optional): NCHW fp32 [B][C][HW]; x: NCHW fp32, updated in place when do_step. */
+int fd_composite_step_f32(float* x, const float* eps_nhwc, const float* weights, float* eps_out, int B, int C,
+                          int HW, int ld, int n_entities, int cfg, float guidance, float c1, float c2, float c3,
+                          float c4, int v_prediction, int do_step, void* stream);
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
