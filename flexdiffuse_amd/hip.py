@@ -86,6 +86,8 @@ _SIGNATURES = {
     'fd_region_blend_f32': (c_int, [P, P] + [c_int] * 7 + [c_float, P]),
     'fd_composite_step_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                       c_float, c_float, c_float, c_int, c_int, P]),
+    'fd_cfg_ddim_masked_step_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                            c_float, c_float, c_float, c_int, c_float, c_float, P]),
     'fd_cast_f32_to_f16': (c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

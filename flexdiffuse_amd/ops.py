@@ -905,6 +905,26 @@ def cfg_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: 
              float(coef[2]), float(coef[3]), int(v_prediction), int(do_step), hip.stream())
 
 
+def cfg_ddim_masked_step(x: torch.Tensor, eps_nhwc: Optional[torch.Tensor], z0: torch.Tensor, noise: torch.Tensor,
+                         mask: torch.Tensor, B: int, C: int, HW: int, cfg: bool = False, guidance: float = 1.0,
+                         coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False, k1: float = 1.0, k2: float = 0.0):
+    '''Masked img2img step (fd_cfg_ddim_masked_step_f32), in place on x (NCHW fp32): with eps_nhwc the CFG + DDIM update of
+    `cfg_ddim_step`, then the blend  known = k1 z0 + k2 noise; x = x' (mask 1) | known (mask 0) | known + mask (x' - known);
+    with eps_nhwc None the blend alone on the x' that x already holds.  mask: fp32 [HW], 1 = repaint, 0 = keep.'''
+    for t in (x, z0, noise):
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW, (tuple(t.shape), B, C, HW)
+    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == HW, (tuple(mask.shape), HW)
+    ld = 0
+    if eps_nhwc is not None:
+        rows = (2 if cfg else 1) * B * HW
+        assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
+        assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
+        ld = eps_nhwc.stride(0)
+    hip.call('fd_cfg_ddim_masked_step_f32', x.data_ptr(), _p(eps_nhwc), z0.data_ptr(), noise.data_ptr(), mask.data_ptr(),
+             B, C, HW, ld, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
+             int(v_prediction), float(k1), float(k2), hip.stream())
+
+
 def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
                    HW: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                    do_step: bool = True, eps_out: Optional[torch.Tensor] = None):

@@ -14,6 +14,11 @@ its ~310 C-ABI launches recorded once per (shape, context) and re-issued each st
 library call -- the same eager launches in the same order, without the Python front's per-op
 work.  Same kernels, same order, bit-identical results in all three modes.
 
+Masked img2img (`mask_image=`, beyond the reference; pipeline/inpaint.py): after every step the kept
+region of the latents is put back on the re-noised init latents -- inside the fused step's own launch
+(fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
+everywhere else.  Without a mask no path changes.
+
 Deliberate differences: E6 initial noise is drawn on the generator's own
 device -- pass a CPU generator for results independent of the GPU count; E8 `init_image`
 is tested with `is not None`.
@@ -33,6 +38,7 @@ from .. import hip, ops
 from ..encode.clip import preprocess
 from ..scheduler import DDIMScheduler, LMSDiscreteScheduler
 from .guide import GuideBase, SimpleGuide
+from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
 VAE_SCALE = 0.18215
 
@@ -283,19 +289,32 @@ class FlexPipeline():
                  return_dict: bool = True,
                  debug: bool = False,
                  latents: Optional[torch.Tensor] = None,
-                 noise: Optional[torch.Tensor] = None):
+                 noise: Optional[torch.Tensor] = None,
+                 mask_image=None):
         '''Arguments and defaults of pipeline/flex.py:127-137, plus two optional tensors for sharded
         runs (flexdiffuse_amd.dist): `latents` -- txt2img initial latents (B,4,h,w) instead of the
         pipeline's own randn; `noise` -- img2img add_noise rows (B,4,h,w) instead of its own randn
-        (the rank's rows of the global batch's draw, `dist.global_img2img_noise`).'''
+        (the rank's rows of the global batch's draw, `dist.global_img2img_noise`).
+
+        `mask_image` (beyond the reference; needs `init_image`): masked img2img / inpainting.  A 2-D map over the
+        init image in image pixels (array-like, tensor, or PIL image resized like the init image), 1 = repaint,
+        0 = keep, shared by the samples of the call.  Reduced to latent resolution (`inpaint.latent_mask`); after
+        every scheduler step the kept region of the latents is put back on the clean init latents re-noised with
+        the call's own noise to the step's level (`inpaint.known_coefficients`), on the last step on the clean init
+        latents themselves.  The image is the VAE decode of the blended latents: pasting the original pixels back
+        over the kept region is out of scope, as are per-sample masks and feathering helpers.'''
         if strength < 0 or strength > 1:
             raise ValueError(
                 f'The value of strength should in [0.0, 1.0] but is {strength}')
+        if mask_image is not None and init_image is None:
+            raise ValueError('mask_image needs an init_image: the mask says which part of it to keep')
         batch_size = guide.batch_size
         self.scheduler.set_timesteps(guide.steps)
         assert self.scheduler.timesteps is not None
 
         if init_image is not None:
+            if mask_image is not None:
+                mask_hw = image_size(init_image)
             if not isinstance(init_image, torch.Tensor):
                 init_image = preprocess(init_image)
             init_image = init_image.to(self.device)
@@ -316,6 +335,15 @@ class FlexPipeline():
                 else noise.to(self.device, torch.float32)
             if tuple(noise.shape) != tuple(init_latents.shape):
                 raise ValueError(f'noise {tuple(noise.shape)} does not match the latents {tuple(init_latents.shape)}')
+            if mask_image is not None:
+                # z0 and n stay alive for the loop; add_noise returns a new tensor, so neither aliases the latents
+                mask_z0, mask_n = init_latents.to(torch.float32).contiguous(), noise.contiguous()
+                h, w = mask_z0.shape[-2:]
+                if mask_hw[0] % h or mask_hw[1] % w or mask_hw[0] // h != mask_hw[1] // w:
+                    raise ValueError(f'init image {mask_hw} is not a whole multiple of its latents {(h, w)}')
+                # uploaded once per call, as z0 and n are
+                mask_dev = latent_mask(mask_image, mask_hw[0], mask_hw[1], mask_hw[0] // h).to(self.device)
+                mask_start = start_level(self.scheduler, int(t_noise[0]))
             init_latents = self.scheduler.add_noise(init_latents, noise, t_noise)
             t_start = max(guide.steps - init_timestep + offset, 0)
         else:
@@ -352,6 +380,7 @@ class FlexPipeline():
             # persistent latent buffer: the captured UNet graph / recorded plan reads this address
             latents = self.loop_latents(latents)
         is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
+        known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
         self._temb_tab = None
         if (fused or planned) and hasattr(self.unet, 'time_bias_table'):
             # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
@@ -382,6 +411,13 @@ class FlexPipeline():
                     vpred = self.scheduler.config['prediction_type'] == 'v_prediction'
                     if comp:
                         guide.step(latents, eps, coef, vpred)
+                        if known is not None:
+                            ops.cfg_ddim_masked_step(latents, None, mask_z0, mask_n, mask_dev, B, C, H * W,
+                                                     k1=known[i][0], k2=known[i][1])
+                    elif known is not None:
+                        # CFG + DDIM update + known-region blend in the one launch of the unmasked step
+                        ops.cfg_ddim_masked_step(latents, eps, mask_z0, mask_n, mask_dev, B, C, H * W, cfg,
+                                                 guide.guidance, coef, vpred, known[i][0], known[i][1])
                     else:
                         ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
                 else:
@@ -403,6 +439,11 @@ class FlexPipeline():
                         noise_pred = guide.noise_pred(model_input, t)
                     latents = self.scheduler.step(noise_pred, t_index, latents,
                                                   **extra_step_kwargs).prev_sample
+                    if known is not None:
+                        # blend the step's own result (not the persistent buffer, which holds the model input)
+                        latents = latents.to(self.device, torch.float32).contiguous()
+                        ops.cfg_ddim_masked_step(latents, None, mask_z0, mask_n, mask_dev, B, C, H * W,
+                                                 k1=known[i][0], k2=known[i][1])
                 if all_latents is not None:
                     all_latents.append(latents)
             # the fused loop ran on the persistent per-shape buffer, which the next call overwrites:

@@ -114,13 +114,14 @@ class Runner():
         return seed
 
     def _run(self, batches: int, guide: GuideBase, init_image, init_size: Tuple[int, int],
-             strength: float, debug: bool):
+             strength: float, debug: bool, mask_image=None):
         '''`batches` sequential pipeline calls on one generator stream -- the reference's only
         data-parallel axis (utils.py:90) -- and the grid of everything they produced.'''
         images: List[Any] = []
+        extra = {'mask_image': mask_image} if mask_image is not None else {}
         for _ in range(batches):
             result = self.pipe(guide=guide, init_image=init_image, init_size=init_size, strength=strength,
-                               generator=self.generator, eta=self.eta, debug=debug)
+                               generator=self.generator, eta=self.eta, debug=debug, **extra)
             images += list(result['sample'])
         return images, image_grid(images)
 
@@ -143,13 +144,16 @@ class Runner():
             guidance_scale: float = 8,
             samples: int = 1,
             seed: Optional[int] = None,
-            debug: bool = False):
-        '''Same arguments and defaults as utils.py:114-133; returns (images, grid).'''
+            debug: bool = False,
+            *,
+            mask_image=None):
+        '''Same arguments and defaults as utils.py:114-133; returns (images, grid).  Beyond the
+        reference: `mask_image` over `init_image` (1 = repaint, 0 = keep; `FlexPipeline.__call__`).'''
         given = locals()
         self._set_seed(seed)
         embeds = self.guide.embeds(prompt=prompt, guide=guide, **{k: given[k] for k in _EMBEDS_KEYS})
         return self._run(samples, SimpleGuide(self.encoder, self.pipe.unet, guidance_scale, steps, embeds),
-                         init_image, init_size, strength, debug)
+                         init_image, init_size, strength, debug, **({'mask_image': mask_image} if mask_image is not None else {}))
 
     def compose(self,
                 bg_prompt: str = '',
@@ -167,13 +171,15 @@ class Runner():
                 debug: bool = False,
                 *,
                 batch_size: int = 1,
-                masks: Optional[Sequence[Any]] = None):
+                masks: Optional[Sequence[Any]] = None,
+                mask_image=None):
         '''Same arguments and defaults as utils.py:168-181; returns (images, grid).  `entities_df`
         rows are [prompt, offset_x, offset_y, width, height, blend]; a DataFrame is taken through
         its `_values` (utils.py:198-199); rows that do not parse or have an empty prompt are dropped.
         Beyond the reference: `batch_size` samples per pipeline call (one UNet forward; `batches *
         batch_size` images in all) and `masks`, aligned with the table rows (None: the rectangle),
-        each an EntitySchema mask over its box.'''
+        each an EntitySchema mask over its box; `mask_image` over `init_image` (1 = repaint, 0 = keep:
+        masked img2img, `FlexPipeline.__call__`).'''
         self._set_seed(seed)
         table = getattr(entities_df, '_values', entities_df)
         parsed = [entity_from_row(row) for row in table]
@@ -186,4 +192,6 @@ class Runner():
         self.last_schema = Schema(bg_prompt, start_style, end_style, style_blend, entities)
         extra = {'batch_size': batch_size} if batch_size != 1 else {}
         guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps, **extra)
-        return self._run(batches, guide, init_image, init_size, strength, debug)
+        # (only when given: a subclass's `_run` with the reference's six arguments keeps working)
+        return self._run(batches, guide, init_image, init_size, strength, debug,
+                         **({'mask_image': mask_image} if mask_image is not None else {}))

@@ -461,6 +461,18 @@ int fd_region_blend_f32(float* dst, const float* src, int C, int H, int W, int o
 int fd_composite_step_f32(float* x, const float* eps_nhwc, const float* weights, float* eps_out, int B, int C,
                           int HW, int ld, int n_entities, int cfg, float guidance, float c1, float c2, float c3,
                           float c4, int v_prediction, int do_step, void* stream);
+/* Masked img2img (inpainting) on the device loop, one launch per step: outside the mask the latents are put back on
+ * the clean init latents z0, re-noised with the call's noise to the level of the step's output.  Per NCHW element,
+ * with m = mask[p] (fp32 [HW], shared by the C channels and the B samples):
+ *   known = k1 z0 + k2 noise ;  x <- x' where m == 1, known where m == 0, known + m (x' - known) otherwise
+ * (fp32, every operation rounded separately; the two exact branches make an all-ones mask give the unmasked step's
+ * bits and an all-zeros mask those of fd_axpby_f32(z0, noise, k1, k2)).  eps_nhwc != NULL (fused form): x' is the
+ * CFG + DDIM (eta = 0) update of fd_cfg_ddim_step_f32 with do_step -- same arguments, same bits -- of the x read.
+ * eps_nhwc == NULL (blend only): x' is x as it stands (any scheduler, any guide); ld, cfg, guidance, c1..c4 and
+ * v_prediction are ignored.  x, z0, noise: NCHW fp32 [B][C][HW]; x is updated in place and may alias neither. */
+int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise, const float* mask,
+                                int B, int C, int HW, int ld, int cfg, float guidance, float c1, float c2, float c3,
+                                float c4, int v_prediction, float k1, float k2, void* stream);
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
