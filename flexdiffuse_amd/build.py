@@ -8,7 +8,7 @@ import torch
 
 from . import weights as W
 from .clip import CLIPModel
-from .scheduler import DDIMScheduler, LMSDiscreteScheduler, PNDMScheduler
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler, PNDMScheduler
 from .tokenizer import SyntheticTokenizer
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
@@ -175,8 +175,9 @@ def load_tokenizer(tokenizer_dir: str, text_cleanup: str = 'fast'):
 def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
     '''The scheduler the checkpoint itself ships (`sd_dir`/scheduler/scheduler_config.json), which is what the
     reference passes into its pipeline (utils.py:70: `sd.scheduler` -- PNDM/PLMS for CompVis/stable-diffusion-v1-4, so a
-    50-step request is 51 UNet evaluations).  `_class_name` -> PNDMScheduler / LMSDiscreteScheduler / DDIMScheduler with the
-    betas, `skip_prk_steps`, `steps_offset`, `set_alpha_to_one`, `clip_sample` of the file.  None when the checkpoint has
+    50-step request is 51 UNet evaluations).  `_class_name` -> PNDMScheduler / LMSDiscreteScheduler / DDIMScheduler /
+    DPMSolverMultistepScheduler with the betas, `skip_prk_steps`, `steps_offset`, `set_alpha_to_one`, `clip_sample`,
+    `solver_order`, `lower_order_final` of the file.  None when the checkpoint has
     no scheduler folder; NotImplementedError for a class this package does not provide (never a silent substitute).'''
     import json
     import os
@@ -205,8 +206,19 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
         extra = {'clip_sample': cfg.get('clip_sample', True), 'set_alpha_to_one': cfg.get('set_alpha_to_one', True),
                  'steps_offset': cfg.get('steps_offset', 0)}
         return DDIMScheduler(**common, **extra, prediction_type=ptype)
+    if name == 'DPMSolverMultistepScheduler':
+        # DPM-Solver++ (2M), midpoint form, on the linspace grid is what is provided; every other variant the file can ask
+        # for is refused by the key that asks for it
+        for key, default, ok in (('algorithm_type', 'dpmsolver++', ('dpmsolver++',)), ('solver_type', 'midpoint', ('midpoint',)),
+                                 ('solver_order', 2, (1, 2)), ('thresholding', False, (False,)),
+                                 ('use_karras_sigmas', False, (False,)), ('timestep_spacing', 'linspace', ('linspace',))):
+            if cfg.get(key, default) not in ok:
+                raise NotImplementedError(f'{path}: DPMSolverMultistepScheduler with {key}={cfg[key]!r} is not provided '
+                                          f'(only {", ".join(repr(v) for v in ok)}); pass scheduler= to choose one explicitly')
+        return DPMSolverMultistepScheduler(**common, solver_order=cfg.get('solver_order', 2), prediction_type=ptype,
+                                           lower_order_final=cfg.get('lower_order_final', True))
     raise NotImplementedError(f'{path}: scheduler class {name!r} is not provided (PNDMScheduler, LMSDiscreteScheduler, '
-                              'DDIMScheduler are); pass scheduler= to choose one explicitly')
+                              'DDIMScheduler, DPMSolverMultistepScheduler are); pass scheduler= to choose one explicitly')
 
 
 def from_directories(sd_dir: str, clip_dir: str, tokenizer_dir: Optional[str] = None, preset: str = 'sd15',

@@ -88,6 +88,8 @@ _SIGNATURES = {
                                       c_float, c_float, c_float, c_int, c_int, P]),
     'fd_cfg_ddim_masked_step_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                             c_float, c_float, c_float, c_int, c_float, c_float, P]),
+    'fd_cfg_multistep_step_f32': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                          c_float, c_float, c_float, c_float, c_float, c_float, P]),
     'fd_cast_f32_to_f16': (c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

@@ -925,6 +925,28 @@ def cfg_ddim_masked_step(x: torch.Tensor, eps_nhwc: Optional[torch.Tensor], z0: 
              int(v_prediction), float(k1), float(k2), hip.stream())
 
 
+def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor], B: int,
+                       C: int, HW: int, cfg: bool, guidance: float, coef, mask=None):
+    '''DPM-Solver++ step (fd_cfg_multistep_step_f32), in place on x (NCHW fp32): e = CFG(eps_nhwc); m0 = p x + q e -> m0_out;
+    x' = a x + w0 m0 (+ w1 m1 when m1 is given), coef = (p, q, a, w0, w1); with mask = (z0, noise, mask [HW], k1, k2) the
+    known-region blend of `cfg_ddim_masked_step` on x'.'''
+    for t in (x, m0_out, m1):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW), (B, C, HW)
+    rows = (2 if cfg else 1) * B * HW
+    assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
+    assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
+    z0 = noise = mk = None
+    k1, k2 = 1.0, 0.0
+    if mask is not None:
+        z0, noise, mk, k1, k2 = mask
+        for t in (z0, noise):
+            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW, (tuple(t.shape), B, C, HW)
+        assert mk.dtype == torch.float32 and mk.is_contiguous() and mk.numel() == HW, (tuple(mk.shape), HW)
+    hip.call('fd_cfg_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(z0), _p(noise),
+             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
+             float(coef[3]), float(coef[4]), float(k1), float(k2), hip.stream())
+
+
 def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
                    HW: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                    do_step: bool = True, eps_out: Optional[torch.Tensor] = None):

@@ -14,6 +14,10 @@ its ~310 C-ABI launches recorded once per (shape, context) and re-issued each st
 library call -- the same eager launches in the same order, without the Python front's per-op
 work.  Same kernels, same order, bit-identical results in all three modes.
 
+DPM-Solver++ (`DPMSolverMultistepScheduler`, beyond the reference's pinned diffusers): SimpleGuide runs the same device
+loop with fd_cfg_multistep_step_f32 as its one launch after the UNet (CFG, x0, history write, second-order multistep
+update, and the known-region blend of a masked request); a device CompositeGuide takes the planned route below.
+
 Masked img2img (`mask_image=`, beyond the reference; pipeline/inpaint.py): after every step the kept
 region of the latents is put back on the re-noised init latents -- inside the fused step's own launch
 (fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
@@ -36,7 +40,7 @@ import torch
 
 from .. import hip, ops
 from ..encode.clip import preprocess
-from ..scheduler import DDIMScheduler, LMSDiscreteScheduler
+from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler
 from .guide import GuideBase, SimpleGuide
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
@@ -371,18 +375,22 @@ class FlexPipeline():
         fused = (device_guide
                  and isinstance(self.scheduler, DDIMScheduler) and not eta
                  and hasattr(self.unet, 'forward_nhwc'))
+        # SimpleGuide + DPM-Solver++: the same loop, its step (CFG, x0, history, multistep update, known-region blend) one
+        # fd_cfg_multistep_step_f32 launch; `eta` does not apply to it
+        fused_ms = (type(guide).noise_pred is SimpleGuide.noise_pred and isinstance(self.scheduler, DPMSolverMultistepScheduler)
+                    and hasattr(self.unet, 'forward_nhwc'))
         B, C, H, W = latents.shape
         # SimpleGuide with ANY other scheduler (PNDM -- what the reference's Runner passes, utils.py:70 -- LMS, DDIM with
         # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
-        planned = (not fused and device_guide and hasattr(self.unet, 'forward_nhwc')
+        planned = (not fused and not fused_ms and device_guide and hasattr(self.unet, 'forward_nhwc')
                    and (self.use_graph or self.use_plan) and not debug)
-        if fused and (self.use_graph or self.use_plan) and not debug:
+        if (fused or fused_ms) and (self.use_graph or self.use_plan) and not debug:
             # persistent latent buffer: the captured UNet graph / recorded plan reads this address
             latents = self.loop_latents(latents)
         is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
         known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
         self._temb_tab = None
-        if (fused or planned) and hasattr(self.unet, 'time_bias_table'):
+        if (fused or fused_ms or planned) and hasattr(self.unet, 'time_bias_table'):
             # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
             # instead of three GEMMs per step
             ts = [float(t) for t in self.scheduler.timesteps[t_start:]]
@@ -420,6 +428,17 @@ class FlexPipeline():
                                                  guide.guidance, coef, vpred, known[i][0], known[i][1])
                     else:
                         ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
+                elif fused_ms:
+                    cfg = guide.classifier_free_guidance
+                    rep = 2 if cfg else 1
+                    if debug:
+                        eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(), rep=rep)
+                        latents = latents.clone()
+                    else:
+                        eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
+                    # masked img2img: the blend rides in the step's launch
+                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                    self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
                 else:
                     t_index, model_input = t, latents
                     if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling

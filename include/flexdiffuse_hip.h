@@ -473,6 +473,21 @@ int fd_composite_step_f32(float* x, const float* eps_nhwc, const float* weights,
 int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise, const float* mask,
                                 int B, int C, int HW, int ld, int cfg, float guidance, float c1, float c2, float c3,
                                 float c4, int v_prediction, float k1, float k2, void* stream);
+/* DPM-Solver++ (2M) on the device loop, one launch per step (additive, ABI 12): replaces the CFG combine of
+ * pipeline/guide.py:59-63 (fd_cfg_ddim_step_f32 without do_step) and the chain of fd_axpby_f32 launches a multistep
+ * `scheduler.step` would issue (x0, the update, one per history term), plus the blend-only launch of
+ * fd_cfg_ddim_masked_step_f32 for a masked request.  Per NCHW element, every operation a separately rounded fp32 one:
+ *   e = u + g (t - u) (cfg) ;  m0 = p x + q e -> m0_out ;  x' = a x + w0 m0 ;  x' = x' + w1 m1 (m1 != NULL)
+ *   mask != NULL: known = k1 z0 + k2 noise ;  x <- x' where m == 1, known where m == 0, known + m (x' - known) otherwise
+ * x: NCHW fp32 [B][C][HW], updated in place.  eps_nhwc: the UNet output [(cfg ? 2 : 1) * B][HW][ld] fp32, unconditional
+ * half first, as fd_cfg_ddim_step_f32 reads it (an NCHW eps: B * C one-channel planes, C = 1, ld = 1).  m0_out, m1: NCHW
+ * fp32 history slots (this step's data prediction x0 and the previous step's; m1 == NULL is the first-order step);
+ * m0_out may alias neither x nor m1.  (p, q): x0 from (x, eps) -- (1/alpha_s, -sigma_s/alpha_s) for eps-prediction,
+ * (alpha_s, -sigma_s) for v-prediction.  mask: fp32 [HW] with z0, noise NCHW fp32 that do not alias x (mask == NULL: z0,
+ * noise, k1, k2 are ignored). */
+int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1, const float* z0,
+                              const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
+                              float p, float q, float a, float w0, float w1, float k1, float k2, void* stream);
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
