@@ -36,6 +36,11 @@ void fd_set_error(const char* fmt, ...);
     } while (0)
 
 static inline int fd_cdiv(int a, int b) { return (a + b - 1) / b; }
+// blocks of a 1-D grid-stride launch: one 256-thread block per 256 elements, at most `cap`
+static inline int fd_grid1d(size_t total, int cap) {
+    const size_t blocks = (total + 255) / 256;
+    return (int)(blocks < (size_t)cap ? blocks : (size_t)cap);
+}
 
 // ---- launch plan (fd_plan_*, runtime.hip): while the calling thread records, every launch entry
 // point appends a by-value copy of its own call (stream left open) to the plan.  FD_PLAN(call)

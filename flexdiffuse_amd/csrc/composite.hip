@@ -1,15 +1,16 @@
 // Region-composited guidance on the device loop (CompositeGuide with batched samples and soft
 // entity masks): one launch per denoising step that blends every entity's noise prediction onto
 // the background with a per-cell weight, applies classifier-free guidance and, optionally, the
-// DDIM (eta = 0) update of k_cfg_ddim.  Same rounded intrinsics in the same order as
-// k_region_blend + k_cfg_ddim (elementwise.hip), so a rectangle (weight = blend inside the box)
-// gives the bits of that chain.
-#include "common.h"
+// DDIM (eta = 0) update.  The blend, the CFG combine and the update are the functions of
+// latent_step.h that k_region_blend (elementwise.hip) and k_latent_step (step.hip) call, so a
+// rectangle (weight = blend inside the box) gives the bits of the fd_region_blend_f32 +
+// fd_cfg_ddim_step_f32 chain.
+#include "latent_step.h"
 
 // eps rows: block r of E = cfg + 1 + n blocks ([uncond] [background] [entity 0] ... [entity n-1]),
 // sample b, pixel p -> row (r * B + b) * HW + p, row stride ld.  One thread owns one (b, p) and
-// all C channels; VEC: float4 loads along the channels (C % 4 == 0, ld % 4 == 0, 16-byte base).
-template <bool VEC>
+// all C channels; V = 4: float4 loads along the channels (C % 4 == 0, ld % 4 == 0, 16-byte base).
+template <int V>
 __global__ __launch_bounds__(256) void k_composite_step(float* __restrict__ x, const float* __restrict__ eps,
                                                         const float* __restrict__ wmap, float* __restrict__ eps_out,
                                                         int B, int C, int HW, int ld, int n, int cfg, float gscale,
@@ -21,55 +22,26 @@ __global__ __launch_bounds__(256) void k_composite_step(float* __restrict__ x, c
         const int p = e % HW;
         const int b = e / HW;
         const size_t row = e * ld;                       // (b * HW + p) * ld
-        constexpr int V = VEC ? 4 : 1;
         for (int c0 = 0; c0 < C; c0 += V) {
-            float v[V], u[V];
-            if constexpr (VEC) {
-                const float4 t = *reinterpret_cast<const float4*>(bgb + row + c0);
-                v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
-            } else {
-                v[0] = bgb[row + c0];
-            }
+            float v[V], s[V];
+            fd_ldv<V>(bgb + row + c0, v);
             for (int k = 0; k < n; ++k) {
                 const float w = wmap[(size_t)k * HW + p];
                 if (w == 0.f) continue;                  // outside the box / masked out: exactly the background
-                const float* en = bgb + (size_t)(k + 1) * blk + row + c0;
-                float s[V];
-                if constexpr (VEC) {
-                    const float4 t = *reinterpret_cast<const float4*>(en);
-                    s[0] = t.x; s[1] = t.y; s[2] = t.z; s[3] = t.w;
-                } else {
-                    s[0] = en[0];
-                }
+                fd_ldv<V>(bgb + (size_t)(k + 1) * blk + row + c0, s);
 #pragma unroll
-                for (int j = 0; j < V; ++j) v[j] = __fadd_rn(v[j], __fmul_rn(w, __fsub_rn(s[j], v[j])));
+                for (int j = 0; j < V; ++j) v[j] = fd_lerp(v[j], s[j], w);
             }
             if (cfg) {
-                if constexpr (VEC) {
-                    const float4 t = *reinterpret_cast<const float4*>(eps + row + c0);
-                    u[0] = t.x; u[1] = t.y; u[2] = t.z; u[3] = t.w;
-                } else {
-                    u[0] = eps[row + c0];
-                }
+                fd_ldv<V>(eps + row + c0, s);
 #pragma unroll
-                for (int j = 0; j < V; ++j) v[j] = __fadd_rn(u[j], __fmul_rn(gscale, __fsub_rn(v[j], u[j])));
+                for (int j = 0; j < V; ++j) v[j] = fd_cfg_mix(s[j], v[j], gscale);
             }
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 const size_t o = ((size_t)b * C + c0 + j) * HW + p;     // NCHW
-                const float nv = v[j];
-                if (eps_out) eps_out[o] = nv;
-                if (do_step) {
-                    const float xv = x[o];
-                    float x0, en = nv;
-                    if (vpred) {
-                        x0 = __fsub_rn(__fmul_rn(c2, xv), __fmul_rn(c1, nv));
-                        en = __fadd_rn(__fmul_rn(c2, nv), __fmul_rn(c1, xv));
-                    } else {
-                        x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(c1, nv)), c2);
-                    }
-                    x[o] = __fadd_rn(__fmul_rn(c3, x0), __fmul_rn(c4, en));
-                }
+                if (eps_out) eps_out[o] = v[j];
+                if (do_step) x[o] = fd_ddim_update(x[o], v[j], c1, c2, c3, c4, vpred);
             }
         }
     }
@@ -85,14 +57,13 @@ extern "C" int fd_composite_step_f32(float* x, const float* eps_nhwc, const floa
                  "fd_composite_step_f32: args");
     FD_CHECK_ARG(n_entities == 0 || weights, FD_EINVAL, "fd_composite_step_f32: weights are null");
     FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_composite_step_f32: x is null");
-    const size_t total = (size_t)B * HW;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
+    const int blocks = fd_grid1d((size_t)B * HW, 2048);
     const bool vec = C % 4 == 0 && ld % 4 == 0 && (uintptr_t)eps_nhwc % 16 == 0;
     if (vec)
-        hipLaunchKernelGGL(k_composite_step<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, weights,
+        hipLaunchKernelGGL(k_composite_step<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, weights,
                            eps_out, B, C, HW, ld, n_entities, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
     else
-        hipLaunchKernelGGL(k_composite_step<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, weights,
+        hipLaunchKernelGGL(k_composite_step<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc, weights,
                            eps_out, B, C, HW, ld, n_entities, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
     FD_CHECK_LAUNCH("k_composite_step");
     return FD_OK;

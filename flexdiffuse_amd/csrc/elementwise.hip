@@ -1,9 +1,10 @@
 // Small HBM-bound kernels around the MFMA path: layout conversion between the pipeline's
 // NCHW fp32 latents and the kernels' NHWC fp16 activations, im2col for the few convs whose
 // input-channel count is below one K tile (conv_in 4ch, VAE conv_in, CLIP patch embed),
-// channel concat for the UNet skip connections, the fused classifier-free-guidance + DDIM
-// update, CLIP token/position embedding gathers and the sinusoidal timestep embedding.
-#include "common.h"
+// channel concat for the UNet skip connections, CLIP token/position embedding gathers, the
+// sinusoidal timestep embedding and the CompositeGuide region blend.  (The fused
+// classifier-free-guidance + scheduler update of the latents is step.hip.)
+#include "latent_step.h"
 
 // ---- NCHW fp32 -> NHWC fp16 (optionally replicated `rep` times along batch: CFG) ---------
 __global__ void k_nchw_to_nhwc(const float* __restrict__ x, half_t* __restrict__ y, int B, int C,
@@ -27,7 +28,7 @@ extern "C" int fd_nchw_f32_to_nhwc_f16(const float* x, void* y, int B, int C, in
     FD_CHECK_ARG(x && y && B > 0 && C > 0 && HW > 0 && rep > 0 && c_pad >= C, FD_EINVAL,
                  "fd_nchw_f32_to_nhwc_f16: args");
     const size_t total = (size_t)B * HW * c_pad;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = fd_grid1d(total, 4096);
     hipLaunchKernelGGL(k_nchw_to_nhwc, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x,
                        (half_t*)y, B, C, HW, rep, c_pad, scale);
     FD_CHECK_LAUNCH("k_nchw_to_nhwc");
@@ -137,7 +138,7 @@ extern "C" int fd_nhwc_f32_to_nchw_f32(const float* x, float* y, int B, int C, i
     FD_CHECK_ARG(x && y && B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL,
                  "fd_nhwc_f32_to_nchw_f32: args");
     const size_t total = (size_t)B * C * HW;
-    const int blocks = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    const int blocks = fd_grid1d(total, 4096);
     hipLaunchKernelGGL(k_nhwc_to_nchw, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, B, C,
                        HW, ld, a, b, clamp01);
     FD_CHECK_LAUNCH("k_nhwc_to_nchw");
@@ -179,7 +180,7 @@ extern "C" int fd_im2col_f16(const void* x, void* y, int B, int Hi, int Wi, int 
                  "fd_im2col_f16: args");
     FD_CHECK_ARG(k_pad >= KH * KW * Cin && k_pad % 8 == 0, FD_ESHAPE, "fd_im2col_f16: k_pad");
     const size_t total = (size_t)B * Ho * Wo * k_pad;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_im2col, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)x,
                        (half_t*)y, B, Hi, Wi, Cin, Ho, Wo, KH, KW, stride, pad_t, pad_l, k_pad);
     FD_CHECK_LAUNCH("k_im2col");
@@ -206,7 +207,7 @@ extern "C" int fd_concat_channels_f16(const void* a, const void* b, void* out, i
     FD_CHECK_ARG(a && b && out && M > 0, FD_EINVAL, "fd_concat_channels_f16: args");
     FD_CHECK_ARG(Ca % 8 == 0 && Cb % 8 == 0, FD_ESHAPE, "fd_concat_channels_f16: C %% 8");
     const size_t total = (size_t)M * (Ca + Cb) / 8;
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_concat, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)a,
                        (const uint4*)b, (uint4*)out, (size_t)M, Ca / 8, Cb / 8);
     FD_CHECK_LAUNCH("k_concat");
@@ -246,7 +247,7 @@ extern "C" int fd_repeat_rows_f16(const void* src, int lds, void* dst, int ldd, 
     FD_CHECK_ARG(cols % 8 == 0 && lds % 8 == 0 && ldd % 8 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0, FD_ESHAPE,
                  "fd_repeat_rows_f16: cols / strides must be multiples of 8 and the pointers 16-byte aligned");
     const size_t total = (size_t)rows * (cols / 8);
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_repeat_rows, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)src, (size_t)(lds / 8), (uint4*)dst,
                        (size_t)(ldd / 8), (size_t)rows, cols / 8, rep);
     FD_CHECK_LAUNCH("k_repeat_rows");
@@ -263,64 +264,10 @@ extern "C" int fd_copy2d_f16(const void* src, int lds, void* dst, int ldd, int64
                      (uintptr_t)dst % 16 == 0,
                  FD_ESHAPE, "fd_copy2d_f16: cols / strides must be multiples of 8 and the pointers 16-byte aligned");
     const size_t total = (size_t)rows * (cols / 8);
-    const int blocks = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
+    const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_copy2d, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)src,
                        (size_t)(lds / 8), (uint4*)dst, (size_t)(ldd / 8), (size_t)rows, cols / 8);
     FD_CHECK_LAUNCH("k_copy2d");
-    return FD_OK;
-}
-
-// ---- fused classifier-free guidance + DDIM (eta = 0) update ---------------------------------
-//   eps = u + g (t - u);  x0 = (x - c1 eps) / c2;  x' = c3 x0 + c4 eps      (all fp32, no FMA)
-// eps comes straight from the UNet's NHWC fp32 output [2B or B][HW][ld]; x is NCHW fp32.
-__global__ void k_cfg_ddim(float* __restrict__ x, const float* __restrict__ eps,
-                           float* __restrict__ eps_out, int B, int C, int HW, int ld, int cfg,
-                           float gscale, float c1, float c2, float c3, float c4, int vpred,
-                           int do_step) {
-    const size_t total = (size_t)B * C * HW;
-    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total;
-         e += (size_t)gridDim.x * blockDim.x) {
-        const int p = e % HW;
-        const size_t r = e / HW;
-        const int c = r % C;
-        const int b = r / C;
-        float n;
-        if (cfg) {
-            const float u = eps[((size_t)b * HW + p) * ld + c];
-            const float t = eps[((size_t)(B + b) * HW + p) * ld + c];
-            n = __fadd_rn(u, __fmul_rn(gscale, __fsub_rn(t, u)));
-        } else {
-            n = eps[((size_t)b * HW + p) * ld + c];
-        }
-        if (eps_out) eps_out[e] = n;
-        if (do_step) {
-            const float xv = x[e];
-            float x0, en = n;
-            if (vpred) {
-                x0 = __fsub_rn(__fmul_rn(c2, xv), __fmul_rn(c1, n));
-                en = __fadd_rn(__fmul_rn(c2, n), __fmul_rn(c1, xv));
-            } else {
-                x0 = __fdiv_rn(__fsub_rn(xv, __fmul_rn(c1, n)), c2);
-            }
-            x[e] = __fadd_rn(__fmul_rn(c3, x0), __fmul_rn(c4, en));
-        }
-    }
-}
-
-extern "C" int fd_cfg_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, int B, int C,
-                                    int HW, int ld, int cfg, float guidance, float c1, float c2,
-                                    float c3, float c4, int v_prediction, int do_step,
-                                    void* stream) {
-    FD_PLAN(fd_cfg_ddim_step_f32(x, eps_nhwc, eps_out, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4, v_prediction, do_step, fd_s_));
-    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(eps_nhwc && B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL,
-                 "fd_cfg_ddim_step_f32: args");
-    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_cfg_ddim_step_f32: x is null");
-    const size_t total = (size_t)B * C * HW;
-    const int blocks = (int)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
-    hipLaunchKernelGGL(k_cfg_ddim, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, eps_nhwc,
-                       eps_out, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4, v_prediction, do_step);
-    FD_CHECK_LAUNCH("k_cfg_ddim");
     return FD_OK;
 }
 
@@ -341,7 +288,7 @@ extern "C" int fd_axpby_f32(const float* x, const float* y, float* out, int64_t 
     FD_PLAN(fd_axpby_f32(x, y, out, n, a, b, exp_half_x, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
     FD_CHECK_ARG(x && out && n > 0, FD_EINVAL, "fd_axpby_f32: args");
-    const int blocks = (int)((n + 255) / 256 < 2048 ? (n + 255) / 256 : 2048);
+    const int blocks = fd_grid1d((size_t)n, 2048);
     hipLaunchKernelGGL(k_axpby, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, y, out,
                        (size_t)n, a, b, exp_half_x);
     FD_CHECK_LAUNCH("k_axpby");
@@ -437,7 +384,7 @@ extern "C" int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stre
     FD_PLAN(fd_cast_f32_to_f16(x, y, n, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
     FD_CHECK_ARG(x && y && n > 0, FD_EINVAL, "fd_cast_f32_to_f16: args");
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = fd_grid1d((size_t)n, 4096);
     hipLaunchKernelGGL(k_cast, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, (half_t*)y,
                        (size_t)n);
     FD_CHECK_LAUNCH("k_cast");
@@ -454,7 +401,7 @@ extern "C" int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stre
     FD_PLAN(fd_cast_f16_to_f32(x, y, n, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
     FD_CHECK_ARG(x && y && n > 0, FD_EINVAL, "fd_cast_f16_to_f32: args");
-    const int blocks = (int)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const int blocks = fd_grid1d((size_t)n, 4096);
     hipLaunchKernelGGL(k_cast_back, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)x, y, (size_t)n);
     FD_CHECK_LAUNCH("k_cast_back");
@@ -469,8 +416,7 @@ __global__ void k_region_blend(float* __restrict__ dst, const float* __restrict_
     for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < total; e += gridDim.x * blockDim.x) {
         const int x = e % sw, y = (e / sw) % sh, c = e / (sw * sh);
         const size_t i = ((size_t)c * H + oy + y) * W + ox + x;
-        const float b = dst[i];
-        dst[i] = __fadd_rn(b, __fmul_rn(blend, __fsub_rn(src[i], b)));
+        dst[i] = fd_lerp(dst[i], src[i], blend);
     }
 }
 

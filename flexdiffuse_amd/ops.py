@@ -897,9 +897,26 @@ def concat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+def _check_f32(numel: int, *tensors: Optional[torch.Tensor]):
+    '''Each given tensor (None: an optional argument left out): fp32, contiguous, `numel` elements.'''
+    for t in tensors:
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == numel), \
+            (None if t is None else (t.dtype, tuple(t.shape), t.stride()), numel)
+
+
+def _check_eps_rows(eps_nhwc: torch.Tensor, rows: int, C: int):
+    '''The UNet's NHWC output as the step kernels read it: fp32, 2-D, unit column stride, at least rows x C.'''
+    assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
+    assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
+
+
 def cfg_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, HW: int,
                   cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                   do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
+    '''CFG combine of eps_nhwc (-> eps_out, NCHW fp32, when given) and, with do_step, the DDIM update of x (NCHW fp32, in
+    place): fd_cfg_ddim_step_f32.'''
+    _check_f32(B * C * HW, x, eps_out)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
     hip.call('fd_cfg_ddim_step_f32', _p(x), eps_nhwc.data_ptr(), _p(eps_out), B, C, HW,
              eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]),
              float(coef[2]), float(coef[3]), int(v_prediction), int(do_step), hip.stream())
@@ -911,14 +928,11 @@ def cfg_ddim_masked_step(x: torch.Tensor, eps_nhwc: Optional[torch.Tensor], z0: 
     '''Masked img2img step (fd_cfg_ddim_masked_step_f32), in place on x (NCHW fp32): with eps_nhwc the CFG + DDIM update of
     `cfg_ddim_step`, then the blend  known = k1 z0 + k2 noise; x = x' (mask 1) | known (mask 0) | known + mask (x' - known);
     with eps_nhwc None the blend alone on the x' that x already holds.  mask: fp32 [HW], 1 = repaint, 0 = keep.'''
-    for t in (x, z0, noise):
-        assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW, (tuple(t.shape), B, C, HW)
-    assert mask.dtype == torch.float32 and mask.is_contiguous() and mask.numel() == HW, (tuple(mask.shape), HW)
+    _check_f32(B * C * HW, x, z0, noise)
+    _check_f32(HW, mask)
     ld = 0
     if eps_nhwc is not None:
-        rows = (2 if cfg else 1) * B * HW
-        assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
-        assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
+        _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
         ld = eps_nhwc.stride(0)
     hip.call('fd_cfg_ddim_masked_step_f32', x.data_ptr(), _p(eps_nhwc), z0.data_ptr(), noise.data_ptr(), mask.data_ptr(),
              B, C, HW, ld, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
@@ -930,18 +944,10 @@ def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Te
     '''DPM-Solver++ step (fd_cfg_multistep_step_f32), in place on x (NCHW fp32): e = CFG(eps_nhwc); m0 = p x + q e -> m0_out;
     x' = a x + w0 m0 (+ w1 m1 when m1 is given), coef = (p, q, a, w0, w1); with mask = (z0, noise, mask [HW], k1, k2) the
     known-region blend of `cfg_ddim_masked_step` on x'.'''
-    for t in (x, m0_out, m1):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW), (B, C, HW)
-    rows = (2 if cfg else 1) * B * HW
-    assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
-    assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
-    z0 = noise = mk = None
-    k1, k2 = 1.0, 0.0
-    if mask is not None:
-        z0, noise, mk, k1, k2 = mask
-        for t in (z0, noise):
-            assert t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW, (tuple(t.shape), B, C, HW)
-        assert mk.dtype == torch.float32 and mk.is_contiguous() and mk.numel() == HW, (tuple(mk.shape), HW)
+    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * HW, x, m0_out, m1, z0, noise)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
     hip.call('fd_cfg_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(z0), _p(noise),
              _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
              float(coef[3]), float(coef[4]), float(k1), float(k2), hip.stream())
@@ -953,13 +959,9 @@ def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: O
     '''CompositeGuide step (fd_composite_step_f32): eps_nhwc [(cfg + 1 + n) * B * HW][ld] fp32 in rep-major order,
     weights [n][HW] fp32 (None: no entity) -> blend, CFG, optionally the DDIM update of x (NCHW fp32, in place).'''
     n = 0 if weights is None else weights.shape[0]
-    rows = ((1 if cfg else 0) + 1 + n) * B * HW
-    assert eps_nhwc.dtype == torch.float32 and eps_nhwc.dim() == 2 and eps_nhwc.stride(1) == 1
-    assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
-    if weights is not None:
-        assert weights.dtype == torch.float32 and weights.is_contiguous() and weights[0].numel() == HW
-    for t in (x, eps_out):
-        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == B * C * HW)
+    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * HW, C)
+    _check_f32(n * HW, weights)
+    _check_f32(B * C * HW, x, eps_out)
     hip.call('fd_composite_step_f32', _p(x), eps_nhwc.data_ptr(), _p(weights), _p(eps_out), B, C, HW,
              eps_nhwc.stride(0), n, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
              float(coef[3]), int(v_prediction), int(do_step), hip.stream())

@@ -23,6 +23,10 @@ region of the latents is put back on the re-noised init latents -- inside the fu
 (fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
 everywhere else.  Without a mask no path changes.
 
+fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 are one kernel (csrc/step.hip) over one
+statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
+wherever they compute the same thing.
+
 Deliberate differences: E6 initial noise is drawn on the generator's own
 device -- pass a CPU generator for results independent of the GPU count; E8 `init_image`
 is tested with `is not None`.
@@ -398,14 +402,20 @@ class FlexPipeline():
             for t in ts:
                 keys.setdefault(t, len(keys))
             self._temb_tab = (keys, self.unet.time_bias_table(list(keys)))
+        # loop-invariant: the CFG switch and the UNet's batch replication of a device guide, DDIM's prediction type
+        cfg = guide.classifier_free_guidance if device_guide else None
+        rep = guide.rep if comp else 2 if cfg else 1
+        vpred = fused and self.scheduler.config['prediction_type'] == 'v_prediction'
+
+        def blend_known(x, i):
+            # masked img2img behind any scheduler / guide: the blend-only launch on the step's result
+            ops.cfg_ddim_masked_step(x, None, mask_z0, mask_n, mask_dev, B, C, H * W, k1=known[i][0], k2=known[i][1])
         # The host only has to stay ahead of the device queue.  A generation-2 collection of the
         # cyclic GC walks every tracked object of the process (~175 k with the SD1.5 weights:
         # ~40 ms) and drains that queue, so collections wait until the images are decoded.
         with (_gc_paused() if self.pause_gc else contextlib.nullcontext()):
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps[t_start:])):
                 if fused:
-                    cfg = guide.classifier_free_guidance
-                    rep = guide.rep if comp else 2 if cfg else 1
                     if debug:
                         # (a composite reads the request's time-bias table as the graph / plan do: bit-equal to them)
                         temb = self._temb_row(int(t)).expand(B * rep, -1).contiguous() if comp and self._temb_tab else None
@@ -416,12 +426,10 @@ class FlexPipeline():
                     coef = self.scheduler.step_coefficients(int(t))[:4]
                     if debug:
                         latents = latents.clone()
-                    vpred = self.scheduler.config['prediction_type'] == 'v_prediction'
                     if comp:
                         guide.step(latents, eps, coef, vpred)
                         if known is not None:
-                            ops.cfg_ddim_masked_step(latents, None, mask_z0, mask_n, mask_dev, B, C, H * W,
-                                                     k1=known[i][0], k2=known[i][1])
+                            blend_known(latents, i)
                     elif known is not None:
                         # CFG + DDIM update + known-region blend in the one launch of the unmasked step
                         ops.cfg_ddim_masked_step(latents, eps, mask_z0, mask_n, mask_dev, B, C, H * W, cfg,
@@ -429,8 +437,6 @@ class FlexPipeline():
                     else:
                         ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
                 elif fused_ms:
-                    cfg = guide.classifier_free_guidance
-                    rep = 2 if cfg else 1
                     if debug:
                         eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(), rep=rep)
                         latents = latents.clone()
@@ -446,9 +452,7 @@ class FlexPipeline():
                         sigma = float(self.scheduler.sigmas[t_index])
                         model_input = ops.axpby(latents, None, 1.0 / ((sigma ** 2 + 1) ** 0.5), 0.0)
                     if planned:
-                        cfg = guide.classifier_free_guidance
-                        eps = self._unet_eps(self.loop_latents(model_input), float(t), guide.stacked_embeds(),
-                                             guide.rep if comp else 2 if cfg else 1)
+                        eps = self._unet_eps(self.loop_latents(model_input), float(t), guide.stacked_embeds(), rep)
                         noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
                         if comp:
                             guide.step(None, eps, eps_out=noise_pred)
@@ -461,8 +465,7 @@ class FlexPipeline():
                     if known is not None:
                         # blend the step's own result (not the persistent buffer, which holds the model input)
                         latents = latents.to(self.device, torch.float32).contiguous()
-                        ops.cfg_ddim_masked_step(latents, None, mask_z0, mask_n, mask_dev, B, C, H * W,
-                                                 k1=known[i][0], k2=known[i][1])
+                        blend_known(latents, i)
                 if all_latents is not None:
                     all_latents.append(latents)
             # the fused loop ran on the persistent per-shape buffer, which the next call overwrites:

@@ -4,7 +4,7 @@ A mask over the init image (image pixels, 1 = repaint, 0 = keep) is reduced to l
 (`latent_mask`); after every scheduler step the kept region of the latents is put back on the
 clean init latents z0, re-noised with the call's own noise n to the level the step's output sits
 at: known = k1 z0 + k2 n, with (k1, k2) from the scheduler's own tables (`known_coefficients`).
-The blend itself is fd_cfg_ddim_masked_step_f32 (csrc/inpaint.hip), driven by FlexPipeline.
+The blend itself is fd_cfg_ddim_masked_step_f32 (csrc/step.hip), driven by FlexPipeline.
 Beyond the reference, whose README names it as the direction of its composition work.
 '''
 from __future__ import annotations

@@ -4,7 +4,7 @@
 
 Tables are numpy float32 like diffusers 0.3.0 (`scaled_linear` betas, cumprod); timesteps
 are integers (bit-exact by construction).  `step` runs the fused HIP update kernel
-(csrc/elementwise.hip k_cfg_ddim); the pipeline's fast path fuses classifier-free guidance
+(csrc/step.hip k_latent_step); the pipeline's fast path fuses classifier-free guidance
 into the same launch.
 '''
 from __future__ import annotations
@@ -285,7 +285,7 @@ class DPMSolverMultistepScheduler(_Configured):
     the list), 1 on the last step when `lower_order_final` and fewer than 15 steps were requested, else `solver_order`.
 
     The whole step -- classifier-free guidance, x0, the history write, the update, optionally the known-region blend of
-    masked img2img -- is one fd_cfg_multistep_step_f32 launch (csrc/multistep.hip).  The history is a device buffer
+    masked img2img -- is one fd_cfg_multistep_step_f32 launch (csrc/step.hip).  The history is a device buffer
     fp32 [2][numel] owned by the scheduler: step i writes slot i & 1 and reads the other.'''
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085,
                  beta_end: float = 0.012, beta_schedule: str = 'scaled_linear', solver_order: int = 2,

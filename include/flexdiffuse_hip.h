@@ -424,7 +424,11 @@ int fd_concat_channels_f16(const void* a, const void* b, void* out, int64_t M, i
  *   eps = u + g (t - u); x0 = (x - c1 eps)/c2; x <- c3 x0 + c4 eps
  * with c1 = sqrt(1-a_t), c2 = sqrt(a_t), c3 = sqrt(a_prev), c4 = sqrt(1-a_prev).
  * x: NCHW fp32 [B][C][HW] updated in place when do_step; eps_nhwc: UNet output
- * [(cfg?2:1)*B][HW][ld] fp32 (unconditional half first); eps_out (optional) NCHW fp32. */
+ * [(cfg?2:1)*B][HW][ld] fp32 (unconditional half first); eps_out (optional) NCHW fp32.
+ * This entry point, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 are ONE kernel (k_latent_step,
+ * csrc/step.hip) over one statement of the arithmetic (csrc/latent_step.h, every operation a separately rounded fp32
+ * one), so they are bit-equal wherever they compute the same thing; float4 along the NCHW planes when HW % 4 == 0 and
+ * the NCHW pointers are 16-byte aligned, scalar otherwise -- the same bits either way. */
 int fd_cfg_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, int B, int C, int HW,
                          int ld, int cfg, float guidance, float c1, float c2, float c3, float c4,
                          int v_prediction, int do_step, void* stream);

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from flexdiffuse_amd.pipeline.guide import GuideBase
-from test_inpaint_host import blend_ref, img2img_request, masked_denoise_ref
+from test_inpaint_host import blend_ref, img2img_request, masked_denoise_ref, step_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -71,19 +71,6 @@ def half_mask(H, W, frac=0.25):
 
 
 # ---- kernel ----------------------------------------------------------------------------------------------------------
-def step_ref(x, eps, B, C, HW, cfg, g, coef, vpred):
-    '''fd_cfg_ddim_step_f32 in fp32 torch on the CPU, in the kernel's operation order.  x: (B, C, HW).'''
-    E = 2 if cfg else 1
-    ev = eps[:E * B * HW, :C].reshape(E, B, HW, C).permute(0, 1, 3, 2)
-    v = ev[0] + torch.tensor(g, dtype=torch.float32) * (ev[1] - ev[0]) if cfg else ev[0]
-    c1, c2, c3, c4 = (torch.tensor(c, dtype=torch.float32) for c in coef)
-    if vpred:
-        x0, en = c2 * x - c1 * v, c2 * v + c1 * x
-    else:
-        x0, en = (x - c1 * v) / c2, v
-    return c3 * x0 + c4 * en
-
-
 def kernel_mask(HW, rng):
     m = torch.rand((HW,), generator=rng)
     m[m < 0.3] = 0.0

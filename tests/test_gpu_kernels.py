@@ -454,6 +454,35 @@ def test_cfg_ddim_and_layout(dev):
     assert float(a.t[:, C:].abs().max()) == 0.0
 
 
+def test_cfg_ddim_step_both_vector_widths(dev):
+    '''fd_cfg_ddim_step_f32 against fp32 torch in the kernel's operation order (`step_ref`, shared with
+    tests/test_gpu_inpaint.py): bit equality, every operation being a separately rounded fp32 one.  HW = 60 with
+    16-byte-aligned pointers: the float4 form of the kernel; HW = 35, and HW = 60 with an x offset by one float: the
+    scalar form.  CFG on and off, eps- and v-prediction, row strides 4, 8 and 5; with do_step = 0 the combined
+    prediction alone goes to eps_out and x is not needed.'''
+    from flexdiffuse_amd import ops
+    from test_inpaint_host import step_ref
+    rng = torch.Generator().manual_seed(0)
+    B, C, g = 3, 4, 7.5
+    coef = (0.6, 0.8, 0.9, 0.43589)
+    for HW, aligned in ((60, True), (35, True), (60, False)):
+        x = torch.randn((B, C, HW), generator=rng)
+        for ld in (4, 8, 5):
+            for cfg in (False, True):
+                eps = torch.randn(((2 if cfg else 1) * B * HW, ld), generator=rng)
+                epsd = eps.to(dev)
+                for vpred in (False, True):
+                    xd = x.to(dev) if aligned else torch.cat([torch.zeros(1), x.flatten()]).to(dev)[1:].view(B, C, HW)
+                    assert xd.is_contiguous() and (xd.data_ptr() % 16 == 0) == aligned
+                    ops.cfg_ddim_step(xd, epsd, B, C, HW, cfg, g, coef, vpred)
+                    assert torch.equal(xd.cpu(), step_ref(x, eps, B, C, HW, cfg, g, coef, vpred)), (HW, aligned, ld, cfg, vpred)
+                # do_step = 0: x' = 0 x0 + 1 e of the eps-prediction update is the combined prediction itself
+                out = torch.full((B, C, HW), float('nan'), device=dev)
+                ops.cfg_ddim_step(None, epsd, B, C, HW, cfg, g, do_step=False, eps_out=out)
+                want = step_ref(torch.zeros((B, C, HW)), eps, B, C, HW, cfg, g, (0.0, 1.0, 0.0, 1.0), False)
+                assert torch.equal(out.cpu(), want), (HW, aligned, ld, cfg)
+
+
 @pytest.mark.parametrize('tile,split', [(1, 1), (2, 1), (3, 1), (4, 1), (5, 1), (6, 1), (1, 2), (2, 4),
                                         (5, 2), (6, 4), (3, 8), (7, 1), (8, 1), (7, 2), (9, 1), (10, 2), (12, 1), (13, 1), (13, 4),
                                         (14, 1), (15, 1), (15, 2), (16, 1), (16, 2), (20, 1), (23, 1), (23, 2)])

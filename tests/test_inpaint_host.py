@@ -36,6 +36,19 @@ def blend_ref(x, z0, n, m, k1, k2):
     return torch.where(m == 1, x, torch.where(m == 0, known, known + m * (x - known)))
 
 
+def step_ref(x, eps, B, C, HW, cfg, g, coef, vpred):
+    '''fd_cfg_ddim_step_f32 in fp32 torch on the CPU, in the kernel's operation order.  x: (B, C, HW).'''
+    E = 2 if cfg else 1
+    ev = eps[:E * B * HW, :C].reshape(E, B, HW, C).permute(0, 1, 3, 2)
+    v = ev[0] + torch.tensor(g, dtype=torch.float32) * (ev[1] - ev[0]) if cfg else ev[0]
+    c1, c2, c3, c4 = (torch.tensor(c, dtype=torch.float32) for c in coef)
+    if vpred:
+        x0, en = c2 * x - c1 * v, c2 * v + c1 * x
+    else:
+        x0, en = (x - c1 * v) / c2, v
+    return c3 * x0 + c4 * en
+
+
 def masked_denoise_ref(sd_unet, ucfg, emb, unc, z0, noise, m, steps, guidance, t_start, t_noise):
     '''z0: clean init latents (B,4,h,w); noise: the call's add_noise tensor; m: fp32 [h][w].'''
     ts, pairs = ref_coefficients(steps, t_start)

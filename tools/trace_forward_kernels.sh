@@ -1,5 +1,5 @@
 #!/bin/bash
-# Kernel sequence of ONE denoising step inside the headline request (between two k_cfg_ddim launches), from a rocprofv3 kernel trace of the bench command:
+# Kernel sequence of ONE denoising step inside the headline request (between two k_latent_step launches: the step kernel of csrc/step.hip), from a rocprofv3 kernel trace of the bench command:
 # names the launches that are not the library's (torch copies / fills).   bash tools/trace_forward_kernels.sh   (on the GPU box)
 R=${GRAFT_REPO_ROOT:-$PWD}
 export PYTHONPATH=$R
@@ -11,10 +11,10 @@ import csv, glob, collections
 f = glob.glob('/tmp/fd_trace/**/*kernel_trace.csv', recursive=True)[0]
 rows = sorted(csv.DictReader(open(f)), key=lambda r: int(r['Start_Timestamp']))
 names = [r['Kernel_Name'] for r in rows]
-idx = [i for i, n in enumerate(names) if n.startswith('k_cfg_ddim')]
+idx = [i for i, n in enumerate(names) if 'k_latent_step<' in n]
 a, b = idx[-3], idx[-2]
 seq = names[a + 1:b + 1]
-print(f'{len(seq)} launches between two k_cfg_ddim launches of the last timed pass')
+print(f'{len(seq)} launches between two k_latent_step launches of the last timed pass')
 c = collections.Counter(n.split('(')[0][:90] for n in seq if not n.startswith(('void k_', 'k_', '_Z')) or 'rocclr' in n or 'at::' in n)
 for k, v in c.items(): print(v, k)
 for i, n in enumerate(seq):
