@@ -10,6 +10,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_cases         # tests/gemm_cases.py (pytest puts the directory of a test module on sys.path)
+
 pytestmark = pytest.mark.gpu
 
 
@@ -507,12 +509,12 @@ def test_gemm_every_tile_and_split(dev, tile, split):
         ops.FORCE_TILE, ops.FORCE_SPLIT = 0, 0
 
 
-def test_gemm_bias_tiles_staged_in_lds(dev):
+def test_gemm_bias_tiles_staged_in_lds(dev, monkeypatch):
     """The DMA kernels stage each tile's bias (and the per-sample bias of single-sample tiles)
     in LDS.  Tile widths that are not a multiple of 64 (160) must not let the last 64-column
     slice spill into the neighbouring buffer: distinct bias values per column, several n-tiles,
     a per-sample bias, persistent and one-shot launches, bit-identical reruns."""
-    from flexdiffuse_amd import ops
+    from flexdiffuse_amd import hip, ops
     B, cin, cout, H = 3, 64, 480, 16                      # 3 n-tiles of 160; tiles lie inside one sample
     x, w = rnd((B, cin, H, H), 1), rnd((cout, cin, 3, 3), 2, (9 * cin) ** -0.5)
     b = torch.arange(cout, dtype=torch.float32) * 0.25 - 40.0
@@ -525,12 +527,26 @@ def test_gemm_bias_tiles_staged_in_lds(dev):
     assert all(torch.equal(outs[0], o) for o in outs)
     # short-K linear with many tiles (persistent kernel: the next tile's bias arrives while the
     # current epilogue reads its own)
-    M, N, K = 8192, 800, 320                               # 5 n-tiles of 160
+    M, N, K = 8192, 1440, 320                              # 32 x 9 tiles of 256x160: more than the 256 one-per-CU slots, so the tiles are walked
     a, wl = rnd((M, K), 5), rnd((N, K), 6, K ** -0.5)
     bl = torch.arange(N, dtype=torch.float32) * 0.125 - 50.0
     wlp = ops.prep_linear(wl, bl, dev)
     ad = a.half().to(dev)
+    descs = []           # the descriptors ops.gemm hands to fd_gemm_f16, as it built them
+
+    def spy(name, *args):
+        if name == 'fd_gemm_f16':
+            descs.append(type(args[0]._obj).from_buffer_copy(args[0]._obj))
+        return call(name, *args)
+
+    call = hip.call
+    monkeypatch.setattr(hip, 'call', spy)
     outs = [ops.gemm(ad, wlp).float().cpu() for _ in range(4)]
+    monkeypatch.setattr(hip, 'call', call)
+    assert len(descs) == 4
+    for d in descs:      # (predicted from the launch rule restated in tests/gemm_cases.py, for the very descriptor of the call)
+        launch = gemm_cases.launch_of_desc(d)
+        assert launch.kernel == 'k_gemm_f16_dmap' and launch.tpl[:2] == (256, 160), launch
     close(outs[0][:, :N], a.half().float() @ wl.half().float().T + bl, rtol=3e-3, atol=3e-2)
     assert all(torch.equal(outs[0], o) for o in outs)
 
