@@ -1,17 +1,22 @@
-// The per-step update of the NCHW fp32 latents on the device loop: ONE kernel behind three entry points.
+// The per-step update of the NCHW fp32 latents on the device loop: ONE kernel behind five entry points.
 //   fd_cfg_ddim_step_f32         CFG combine (-> eps_out) and, with do_step, the DDIM (eta = 0) update
 //   fd_cfg_ddim_masked_step_f32  masked img2img: that step followed by the known-region blend, or (eps == NULL) the blend
 //                                alone on the x' that x already holds (any scheduler, any guide)
 //   fd_cfg_multistep_step_f32    DPM-Solver++ (2M) (Lu et al. 2022, "DPM-Solver++", Algorithm 2): CFG combine, the data
 //                                prediction m0 = p x + q e -> m0_out, x' = a x + w0 m0 (+ w1 m1: order 2), the blend
+//   fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32   the stochastic forms (DDIM eta > 0, SDE-DPM-Solver++):
+//                                the same steps plus x' += sn z, z the counter-based normal stream of philox.h generated
+//                                in the kernel; fd_philox_normal_f32 writes that stream out on its own
 // Per element, in this order, every operation a separately rounded fp32 one (latent_step.h; no FMA):
-//   e = u + g (t - u) (cfg; otherwise the one eps row) -> eps_out ;  the update ;  -> m0_out ;  the blend (mask) ;  -> x
+//   e = u + g (t - u) (cfg; otherwise the one eps row) -> eps_out ;  the update ;  + sn z (sn != 0) ;  -> m0_out ;
+//   the blend (mask) ;  -> x
 // so the entry points are bit-equal to each other wherever they overlap (an all-ones mask is the plain step, an
 // all-zeros mask is fd_axpby_f32(z0, n, k1, k2), the fused form is the plain step + the blend-only form, DPM-Solver++
 // at order 1 is DDIM's arithmetic on other coefficients) and to a torch fp32 restatement in that order.  eps comes straight
 // from the UNet's NHWC fp32 output [(cfg + 1) B][HW][ld]; an NCHW eps is the same call with B C one-channel planes
 // (C = 1, ld = 1).  The coefficients come from the host (the schedulers' step_coefficients, inpaint.known_coefficients).
 #include "latent_step.h"
+#include "philox.h"
 
 enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2 };
 
@@ -23,11 +28,14 @@ struct FdStepArgs {
     const float *m1, *z0, *nz, *mask;
     int B, C, HW, ld, cfg, vpred;
     float g, co[5], k1, k2;
+    float sn;                  // noise coefficient; 0: no noise stage (nz_addr unused)
+    FdNoiseAddr nz_addr;
 };
 
 // One thread owns V consecutive pixels of one (b, c) plane.  V = 4: HW % 4 == 0 and 16-byte bases, so a group never
-// straddles a plane and every NCHW tensor moves as float4; the NHWC eps rows (stride ld) are read per pixel.
-template <int V, int UPDATE>
+// straddles a plane and every NCHW tensor moves as float4; the NHWC eps rows (stride ld) are read per pixel.  NOISE (with
+// V = 4: per % 4 == 0 too, so a group is one Philox block): x' += sn z between the update and the blend.
+template <int V, int UPDATE, bool NOISE>
 __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
     const size_t groups = (size_t)a.B * a.C * a.HW / V;
     const bool use_x = UPDATE != FD_STEP_NONE || a.mask;     // CFG combine alone (-> eps_out): x may be NULL
@@ -67,6 +75,12 @@ __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
             }
             fd_stv<V>(a.m0_out + e, ev);
         }
+        if constexpr (NOISE) {
+            float sv[V];
+            fd_noise_normals<V>(a.nz_addr, e, sv);
+#pragma unroll
+            for (int j = 0; j < V; ++j) xv[j] = __fadd_rn(xv[j], __fmul_rn(a.sn, sv[j]));
+        }
         if (a.mask) {
 #pragma unroll
             for (int j = 0; j < V; ++j) xv[j] = fd_known_blend(xv[j], zv[j], nv[j], mv[j], a.k1, a.k2);
@@ -75,17 +89,21 @@ __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
     }
 }
 
-// V = 4 when HW % 4 == 0 and every NCHW pointer the kernel will touch is 16-byte aligned, else V = 1; grid; launch.
+// V = 4 when HW % 4 == 0 (with noise: per % 4 == 0 too) and every NCHW pointer the kernel will touch is 16-byte aligned,
+// else V = 1; grid; launch.  sn == 0 launches the kernels without the noise stage: today's bits.
 static int fd_latent_step(int update, const FdStepArgs& a, void* stream) {
     uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
     if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
     if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
-    const int vec = a.HW % 4 == 0 && bases % 16 == 0;
-    static void (*const kernels[2][3])(const FdStepArgs) = {
-        {k_latent_step<1, FD_STEP_NONE>, k_latent_step<1, FD_STEP_DDIM>, k_latent_step<1, FD_STEP_MULTISTEP>},
-        {k_latent_step<4, FD_STEP_NONE>, k_latent_step<4, FD_STEP_DDIM>, k_latent_step<4, FD_STEP_MULTISTEP>}};
+    const int noise = update != FD_STEP_NONE && a.sn != 0.f;
+    const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
+    static void (*const kernels[2][2][3])(const FdStepArgs) = {
+        {{k_latent_step<1, FD_STEP_NONE, false>, k_latent_step<1, FD_STEP_DDIM, false>, k_latent_step<1, FD_STEP_MULTISTEP, false>},
+         {k_latent_step<4, FD_STEP_NONE, false>, k_latent_step<4, FD_STEP_DDIM, false>, k_latent_step<4, FD_STEP_MULTISTEP, false>}},
+        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true>, k_latent_step<1, FD_STEP_MULTISTEP, true>},
+         {nullptr, k_latent_step<4, FD_STEP_DDIM, true>, k_latent_step<4, FD_STEP_MULTISTEP, true>}}};
     const size_t groups = (size_t)a.B * a.C * a.HW / (vec ? 4 : 1);
-    hipLaunchKernelGGL(kernels[vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0, (hipStream_t)stream, a);
     FD_CHECK_LAUNCH("k_latent_step");
     return FD_OK;
 }
@@ -98,7 +116,7 @@ extern "C" int fd_cfg_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_
     FD_CHECK_ARG(eps_nhwc && B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_ddim_step_f32: args");
     FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_cfg_ddim_step_f32: x is null");
     const FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, nullptr, nullptr, nullptr, B, C, HW, ld, cfg, v_prediction,
-                          guidance, {c1, c2, c3, c4, 0.f}, 1.f, 0.f};
+                          guidance, {c1, c2, c3, c4, 0.f}, 1.f, 0.f, 0.f, {}};
     return fd_latent_step(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
 }
 
@@ -113,7 +131,7 @@ extern "C" int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, cons
     FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && (!eps_nhwc || ld >= C), FD_EINVAL, "fd_cfg_ddim_masked_step_f32: sizes");
     FD_CHECK_ARG(x != z0 && x != noise, FD_EINVAL, "fd_cfg_ddim_masked_step_f32: z0 / noise alias the latents");
     const FdStepArgs a = {x, eps_nhwc, nullptr, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
-                          guidance, {c1, c2, c3, c4, 0.f}, k1, k2};
+                          guidance, {c1, c2, c3, c4, 0.f}, k1, k2, 0.f, {}};
     return fd_latent_step(eps_nhwc ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
 }
 
@@ -130,6 +148,98 @@ extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float*
     FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_multistep_step_f32: mask without z0 / noise (null)");
     FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_multistep_step_f32: z0 / noise alias the latents");
     const FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
-                          guidance, {p, q, a, w0, w1}, k1, k2};
+                          guidance, {p, q, a, w0, w1}, k1, k2, 0.f, {}};
     return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+}
+
+// ---- the stochastic forms ------------------------------------------------------------------------------------------
+// the noise address of a launch over `total` elements; the checks every noise entry point shares
+static int fd_noise_addr(const char* who, uint64_t seed, int64_t sample_offset, int per, int draw,
+                         int noise_stream, unsigned long long total, FdNoiseAddr* out) {
+    FD_CHECK_ARG(per > 0 && total % (unsigned long long)per == 0, FD_EINVAL,
+                 "%s: sizes: per must be positive and divide the element count", who);
+    FD_CHECK_ARG(sample_offset >= 0 && draw >= 0 && noise_stream >= 0, FD_EINVAL,
+                 "%s: sizes: negative sample_offset, draw or stream", who);
+    FD_CHECK_ARG((unsigned long long)sample_offset + total / (unsigned long long)per <= (1ull << 32), FD_EINVAL,
+                 "%s: sizes: sample index past 2^32", who);
+    *out = {(unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), (unsigned)sample_offset, (unsigned)draw,
+            (unsigned)noise_stream, per};
+    return FD_OK;
+}
+
+extern "C" int fd_cfg_ddim_noise_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise,
+                                          const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
+                                          float c1, float c2, float c3, float c4, int v_prediction, float k1, float k2,
+                                          float sigma, uint64_t seed, int64_t sample_offset, int per, int draw,
+                                          void* stream) {
+    FD_PLAN(fd_cfg_ddim_noise_step_f32(x, eps_nhwc, z0, noise, mask, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4,
+                                       v_prediction, k1, k2, sigma, seed, sample_offset, per, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_cfg_ddim_noise_step_f32: x or eps_nhwc is null");
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_ddim_noise_step_f32: sizes");
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_ddim_noise_step_f32: mask without z0 / noise (null)");
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_ddim_noise_step_f32: z0 / noise alias the latents");
+    FdStepArgs a = {x, eps_nhwc, nullptr, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
+                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
+    const int rc = fd_noise_addr("fd_cfg_ddim_noise_step_f32", seed, sample_offset, per, draw, 0,
+                                 (unsigned long long)B * C * HW, &a.nz_addr);
+    if (rc != FD_OK) return rc;
+    return fd_latent_step(FD_STEP_DDIM, a, stream);
+}
+
+extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
+                                               const float* z0, const float* noise, const float* mask, int B, int C,
+                                               int HW, int ld, int cfg, float guidance, float p, float q, float a,
+                                               float w0, float w1, float k1, float k2, float sn,
+                                               uint64_t seed, int64_t sample_offset, int per, int draw,
+                                               void* stream) {
+    FD_PLAN(fd_cfg_multistep_noise_step_f32(x, eps_nhwc, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, guidance, p, q,
+                                            a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: x, eps_nhwc or m0_out is null");
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: sizes");
+    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: m0_out aliases the latents or m1");
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_multistep_noise_step_f32: mask without z0 / noise (null)");
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_multistep_noise_step_f32: z0 / noise alias the latents");
+    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
+                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
+    const int rc = fd_noise_addr("fd_cfg_multistep_noise_step_f32", seed, sample_offset, per, draw, 0,
+                                 (unsigned long long)B * C * HW, &s.nz_addr);
+    if (rc != FD_OK) return rc;
+    return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+}
+
+// One thread owns one Philox block: elements 4q..4q+3 of one sample, as far as the sample and the buffer reach.
+__global__ __launch_bounds__(256) void k_philox_normal(float* out, size_t n, const FdNoiseAddr a) {
+    const size_t gps = ((size_t)a.per + 3) / 4;                      // groups per sample
+    const size_t groups = (n + a.per - 1) / a.per * gps;
+    for (size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x; g < groups; g += (size_t)gridDim.x * blockDim.x) {
+        const size_t first = g / gps * a.per, q4 = g % gps * 4;     // the sample's first element; the group's inside it
+        if (first + q4 >= n) continue;
+        float z[4];
+        unsigned w[4];
+        fd_noise_words(a, first + q4, w);
+        fd_normal_pair(w[0], w[1], z[0], z[1]);
+        fd_normal_pair(w[2], w[3], z[2], z[3]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (q4 + j < (size_t)a.per && first + q4 + j < n) out[first + q4 + j] = z[j];
+    }
+}
+
+extern "C" int fd_philox_normal_f32(float* out, int64_t n, int per, uint64_t seed, int64_t sample_offset,
+                                    int draw, int noise_stream, void* stream) {
+    FD_PLAN(fd_philox_normal_f32(out, n, per, seed, sample_offset, draw, noise_stream, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(out, FD_EINVAL, "fd_philox_normal_f32: out is null");
+    FD_CHECK_ARG(n > 0 && per > 0, FD_EINVAL, "fd_philox_normal_f32: sizes");
+    FdNoiseAddr a;
+    // the last sample may be partial: the address checks run on the whole samples the buffer touches
+    const unsigned long long samples = ((unsigned long long)n + per - 1) / per;
+    const int rc = fd_noise_addr("fd_philox_normal_f32", seed, sample_offset, per, draw, noise_stream, samples * per, &a);
+    if (rc != FD_OK) return rc;
+    const size_t groups = (size_t)samples * (((size_t)per + 3) / 4);
+    hipLaunchKernelGGL(k_philox_normal, dim3(fd_grid1d(groups, 2048)), dim3(256), 0, (hipStream_t)stream, out, (size_t)n, a);
+    FD_CHECK_LAUNCH("k_philox_normal");
+    return FD_OK;
 }

@@ -47,6 +47,12 @@ def shard_range(rank: int, world_size: int, per_rank: int) -> slice:
     return slice(rank * per_rank, (rank + 1) * per_rank)
 
 
+def sample_offset(rank: int, world_size: int, per_rank: int) -> int:
+    '''Global index of `rank`'s first sample: the `sample_offset` of its `noise.PhiloxNoise` (step noise that does not
+    depend on the world size).'''
+    return shard_range(rank, world_size, per_rank).start
+
+
 def global_noise(total: int, shape: Sequence[int], seed: int) -> torch.Tensor:
     '''The whole global batch of initial latents from ONE host generator (fp32, CPU).'''
     return torch.randn((total,) + tuple(shape), generator=torch.Generator('cpu').manual_seed(seed),

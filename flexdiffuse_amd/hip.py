@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 from typing import Optional
 
 import torch
@@ -90,6 +90,13 @@ _SIGNATURES = {
                                             c_float, c_float, c_float, c_int, c_float, c_float, P]),
     'fd_cfg_multistep_step_f32': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                           c_float, c_float, c_float, c_float, c_float, c_float, P]),
+    'fd_philox_normal_f32': (c_int, [P, c_int64, c_int, c_uint64, c_int64, c_int, c_int, P]),
+    'fd_cfg_ddim_noise_step_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                           c_float, c_float, c_float, c_int, c_float, c_float, c_float, c_uint64, c_int64,
+                                           c_int, c_int, P]),
+    'fd_cfg_multistep_noise_step_f32': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
+                                                c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_uint64,
+                                                c_int64, c_int, c_int, P]),
     'fd_cast_f32_to_f16': (c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

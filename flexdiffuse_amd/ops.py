@@ -953,6 +953,47 @@ def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Te
              float(coef[3]), float(coef[4]), float(k1), float(k2), hip.stream())
 
 
+def philox_normal(out: torch.Tensor, per: int, seed: int, sample_offset: int = 0, draw: int = 0, stream: int = 1) -> torch.Tensor:
+    '''Fill `out` (fp32, contiguous) with the counter-based normal stream (fd_philox_normal_f32): flat element i is element
+    i % per of sample sample_offset + i // per.  The step kernels add the same values (stream 0) without writing them.'''
+    assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() > 0
+    hip.require_device(out)
+    hip.call('fd_philox_normal_f32', out.data_ptr(), out.numel(), int(per), int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample_offset),
+             int(draw), int(stream), hip.stream())
+    return out
+
+
+def cfg_ddim_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, B: int, C: int, HW: int, cfg: bool, guidance: float, coef,
+                        v_prediction: bool, sigma: float, noise, per: int, draw: int, mask=None):
+    '''Stochastic DDIM step (fd_cfg_ddim_noise_step_f32), in place on x (NCHW fp32): the CFG + DDIM update of `cfg_ddim_step`
+    with coef = (c1, c2, c3, c4) of `step_coefficients(t, eta)`, then x' += sigma z with z the stream of `noise` (a
+    `PhiloxNoise`) at (`per` elements per sample, `draw`), generated in the kernel; with mask = (z0, noise, mask [HW], k1, k2)
+    the known-region blend of `cfg_ddim_masked_step` on the result.  sigma == 0: the bits of those two.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * HW, x, z0, nz)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
+    hip.call('fd_cfg_ddim_noise_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(z0), _p(nz), _p(mk), B, C, HW,
+             eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
+             int(v_prediction), float(k1), float(k2), float(sigma), noise.seed, noise.sample_offset, int(per), int(draw),
+             hip.stream())
+
+
+def cfg_multistep_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor],
+                             B: int, C: int, HW: int, cfg: bool, guidance: float, coef, sn: float, noise, per: int,
+                             draw: int, mask=None):
+    '''SDE-DPM-Solver++ step (fd_cfg_multistep_noise_step_f32): `cfg_multistep_step` with x' += sn z after the update, z as
+    in `cfg_ddim_noise_step`.  sn == 0: the bits of `cfg_multistep_step`.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
+    hip.call('fd_cfg_multistep_noise_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(z0), _p(nz),
+             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
+             float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn), noise.seed, noise.sample_offset, int(per),
+             int(draw), hip.stream())
+
+
 def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
                    HW: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                    do_step: bool = True, eps_out: Optional[torch.Tensor] = None):

@@ -23,7 +23,14 @@ region of the latents is put back on the re-noised init latents -- inside the fu
 (fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
 everywhere else.  Without a mask no path changes.
 
-fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 are one kernel (csrc/step.hip) over one
+Stochastic sampling (`pipe.step_noise`, a `noise.PhiloxNoise`; beyond the reference, which forwards `eta` to its scheduler,
+pipeline/flex.py:247-251): with it, SimpleGuide + DDIM + `eta > 0` stays on the device loop -- one fd_cfg_ddim_noise_step_f32 per
+step, the noise a counter-based stream generated inside the kernel -- and `DPMSolverMultistepSDEScheduler` runs the multistep
+loop with fd_cfg_multistep_noise_step_f32; every other route hands the stream's address to `scheduler.step(step_noise=)`.  The
+result depends on (seed, global sample index, step) only: not on the loop mode, the batch split or the rank count.  Without
+`step_noise`, `eta > 0` is the generator route as before.
+
+fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 (and their two noise forms) are one kernel (csrc/step.hip) over one
 statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
 wherever they compute the same thing.
 
@@ -44,7 +51,8 @@ import torch
 
 from .. import hip, ops
 from ..encode.clip import preprocess
-from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler
+from ..noise import PhiloxNoise
+from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler
 from .guide import GuideBase, SimpleGuide
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
@@ -114,6 +122,10 @@ class FlexPipeline():
         # opt-in (bench.py, Runner(pause_gc=True)): keep the cyclic GC off across the denoising loop.
         # Off by default: a drop-in must not change interpreter-global state of someone else's process.
         self.pause_gc = False
+        # opt-in: the address of the request's step noise (noise.PhiloxNoise).  With it `eta > 0` under DDIM runs on the
+        # fused loop and every scheduler that takes `step_noise=` draws from the counter-based stream; None: the
+        # generator route (an SDE scheduler then derives one from the call's generator seed)
+        self.step_noise: Optional[PhiloxNoise] = None
 
     @classmethod
     def from_pretrained(cls, sd_dir, clip_dir=None, tokenizer_dir=None, preset: str = 'sd15',
@@ -375,14 +387,24 @@ class FlexPipeline():
         # UNet forward over its E context blocks (the batch-1 rectangle path stays on the generic protocol)
         comp = (type(guide).noise_pred is CompositeGuide.noise_pred and getattr(guide, 'on_device', False)
                 and hasattr(self.unet, 'forward_nhwc'))
-        device_guide = type(guide).noise_pred is SimpleGuide.noise_pred or comp
+        simple = type(guide).noise_pred is SimpleGuide.noise_pred
+        device_guide = simple or comp
+        # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
+        step_noise = self.step_noise
+        sde = isinstance(self.scheduler, DPMSolverMultistepSDEScheduler)
+        if sde and step_noise is None:
+            step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
+        # eta > 0 stays fused for SimpleGuide when the noise comes from the counter-based stream (fd_cfg_ddim_noise_step_f32)
+        noisy = bool(eta) and step_noise is not None and simple
         fused = (device_guide
-                 and isinstance(self.scheduler, DDIMScheduler) and not eta
+                 and isinstance(self.scheduler, DDIMScheduler) and (not eta or noisy)
                  and hasattr(self.unet, 'forward_nhwc'))
         # SimpleGuide + DPM-Solver++: the same loop, its step (CFG, x0, history, multistep update, known-region blend) one
-        # fd_cfg_multistep_step_f32 launch; `eta` does not apply to it
-        fused_ms = (type(guide).noise_pred is SimpleGuide.noise_pred and isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        # fd_cfg_multistep_step_f32 launch (the SDE form: fd_cfg_multistep_noise_step_f32); `eta` does not apply to it
+        fused_ms = (simple and isinstance(self.scheduler, DPMSolverMultistepScheduler)
                     and hasattr(self.unet, 'forward_nhwc'))
+        # generic and planned routes: a scheduler that takes it draws from the stream at (noise, t_start + i)
+        takes_noise = step_noise is not None and 'step_noise' in inspect.signature(self.scheduler.step).parameters
         B, C, H, W = latents.shape
         # SimpleGuide with ANY other scheduler (PNDM -- what the reference's Runner passes, utils.py:70 -- LMS, DDIM with
         # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
@@ -423,10 +445,16 @@ class FlexPipeline():
                                                      rep=rep, temb=temb)
                     else:
                         eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
-                    coef = self.scheduler.step_coefficients(int(t))[:4]
+                    coef = self.scheduler.step_coefficients(int(t), eta if noisy else 0.0)
+                    sigma, coef = coef[4], coef[:4]
                     if debug:
                         latents = latents.clone()
-                    if comp:
+                    if noisy:
+                        # CFG + DDIM update + sigma z (+ the known-region blend of a masked request) in one launch
+                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                        ops.cfg_ddim_noise_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred, float(sigma),
+                                                step_noise, C * H * W, t_start + i, blend)
+                    elif comp:
                         guide.step(latents, eps, coef, vpred)
                         if known is not None:
                             blend_known(latents, i)
@@ -444,7 +472,11 @@ class FlexPipeline():
                         eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
                     # masked img2img: the blend rides in the step's launch
                     blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                    self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
+                    if sde:
+                        self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend,
+                                                  (step_noise, t_start + i))
+                    else:
+                        self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
                 else:
                     t_index, model_input = t, latents
                     if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling
@@ -460,6 +492,8 @@ class FlexPipeline():
                             ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
                     else:
                         noise_pred = guide.noise_pred(model_input, t)
+                    if takes_noise:
+                        extra_step_kwargs['step_noise'] = (step_noise, t_start + i)
                     latents = self.scheduler.step(noise_pred, t_index, latents,
                                                   **extra_step_kwargs).prev_sample
                     if known is not None:

@@ -101,11 +101,18 @@ class DDIMScheduler(_Configured):
                 np.sqrt(one - a_p - sigma * sigma), sigma)
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, eta: float = 0.0,
-             generator=None, **_):
+             generator=None, step_noise=None, **_):
+        '''`step_noise` = (PhiloxNoise, draw): the eta > 0 term sigma z comes from the counter-based stream (noise.py) inside
+        the update's own launch -- the bits of the fused loop's step.  Without it: one draw of torch's generator per call.'''
         c1, c2, c3, c4, sigma = self.step_coefficients(int(timestep), eta)
         B, C, H, W = sample.shape
         x = sample.to(torch.float32).clone()
         eps = model_output.to(torch.float32).contiguous()
+        if step_noise is not None:
+            ops.cfg_ddim_noise_step(x, eps.view(-1, 1), B * C, 1, H * W, False, 1.0, (c1, c2, c3, c4),
+                                    self.config['prediction_type'] == 'v_prediction', float(sigma), step_noise[0],
+                                    C * H * W, int(step_noise[1]))
+            return SimpleNamespace(prev_sample=x)
         # NCHW eps viewed as B*C single-channel "samples" (ld = 1)
         ops.cfg_ddim_step(x, eps.view(-1, 1), B * C, 1, H * W, False, 1.0, (c1, c2, c3, c4),
                           self.config['prediction_type'] == 'v_prediction')
@@ -406,3 +413,69 @@ class DPMSolverMultistepScheduler(_Configured):
         a = self.alphas_cumprod[t]
         return ops.axpby(original.to(torch.float32), noise.to(torch.float32),
                          float(np.sqrt(a)), float(np.sqrt(np.float32(1.0) - a)))
+
+
+class DPMSolverMultistepSDEScheduler(DPMSolverMultistepScheduler):
+    '''SDE-DPM-Solver++ (2M): the stochastic form of the parent (Lu et al. 2022, "DPM-Solver++", the SDE variant of its
+    multistep data-prediction solver), restated from the exponential-integrator solution of the reverse-time SDE.  PARITY
+    UNPINNED against diffusers' `algorithm_type='sde-dpmsolver++'`, like the parent.
+
+    The reverse-time SDE in data-prediction form,  dx = [f x + (g^2 / sigma^2) (x - alpha x0)] dt + g dw  (f = d ln alpha / dt,
+    g^2 = d sigma^2 / dt - 2 f sigma^2), is linear in x once x0 is held at the history's estimate over the step; its exact
+    solution from s to t (h = lambda_t - lambda_s, E = -expm1(-2h) = 1 - e^{-2h}) is
+        x' = (sigma_t / sigma_s) e^{-h} x  +  alpha_t E x0  +  sigma_t sqrt(E) z ,   z ~ N(0, I)
+    and the second-order (midpoint) form replaces x0 by m0 + (m0 - m1) / (2r), r as the parent.  As coefficients of
+    x' = a x + w0 m0 + w1 m1 + sn z:  a = (sigma_t / sigma_s) e^{-h};  G = alpha_t E;  order 1: (w0, w1) = (G, 0);  order 2:
+    (w0, w1) = (G (1 + 1/(2r)), -G/(2r));  sn = sigma_t sqrt(E);  (p, q) as the parent.  Two identities hold for any step
+    and order: a alpha_s + w0 + w1 = alpha_t (a clean sample stays on the signal level) and a^2 sigma_s^2 + sn^2 =
+    sigma_t^2 (the noise level lands on the table), so the noise levels of masked img2img are the parent's.  At order 1 this is
+    DDIM with eta = 1 on the same timesteps (equivalently an Euler-ancestral step).
+
+    z is the counter-based stream of noise.py generated inside the step's launch (fd_cfg_multistep_noise_step_f32), addressed
+    by `step_noise` = (PhiloxNoise, draw); order rule, history and timesteps are inherited.'''
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        self._internal_dict = _Config(**self._internal_dict, algorithm_type='sde-dpmsolver++')
+
+    def step_coefficients(self, i: int, order: int = 1):
+        '''(p, q, a, w0, w1, sn) float32, computed in float64 (class docstring).'''
+        ts = self.timesteps
+        s = int(ts[i])
+        t = int(ts[i + 1]) if i + 1 < len(ts) else 0
+        al, sg, lm = self.alpha_t, self.sigma_t, self.lambda_t
+        p, q = super().step_coefficients(i, 1)[:2]
+        h = lm[t] - lm[s]
+        E = -np.expm1(-2.0 * h)
+        a = sg[t] / sg[s] * np.exp(-h)
+        G = al[t] * E
+        if order == 1:
+            w0, w1 = G, 0.0
+        elif order == 2:
+            if i < 1:
+                raise ValueError('order 2 needs a previous step')
+            r = (lm[s] - lm[int(ts[i - 1])]) / h
+            w0, w1 = G * (1.0 + 0.5 / r), -G * 0.5 / r
+        else:
+            raise NotImplementedError(f'order {order}')
+        return (p, q) + tuple(np.float32(v) for v in (a, w0, w1, sg[t] * np.sqrt(E)))
+
+    def fused_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
+                   cfg: bool, guidance: float, mask=None, step_noise=None, per: Optional[int] = None):
+        '''The parent's one launch plus sn z.  `step_noise` = (PhiloxNoise, draw), default (PhiloxNoise(0), the step's
+        index); `per`: elements per sample, default C * HW (pass it when (B, C) is a view of the real latent).'''
+        from .noise import PhiloxNoise
+        i = self.step_index(timestep)
+        hist = self._history(latents)
+        order = self.step_order(i)
+        co = self.step_coefficients(i, order)
+        noise, draw = step_noise if step_noise is not None else (PhiloxNoise(0), i)
+        ops.cfg_multistep_noise_step(latents, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C, HW,
+                                     cfg, guidance, co[:5], co[5], noise, C * HW if per is None else per, int(draw), mask)
+        self._last = i
+
+    def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, step_noise=None, **_):
+        B, C, H, W = sample.shape
+        x = sample.to(torch.float32).clone()
+        eps = model_output.to(torch.float32).contiguous()
+        self.fused_step(x, eps.view(-1, 1), timestep, B * C, 1, H * W, False, 1.0, None, step_noise, C * H * W)
+        return SimpleNamespace(prev_sample=x)

@@ -26,7 +26,9 @@ from . import build
 from .encode.clip import CLIPEncoder
 from .guidance import Guide
 from .composition import CompositeGuide, EntitySchema, Schema
+from .noise import PhiloxNoise
 from .pipeline.guide import GuideBase, SimpleGuide
+from .scheduler import DPMSolverMultistepSDEScheduler
 
 MAX_SEED = 2147483647          # the reference clamps seeds to int32 (utils.py:22)
 
@@ -101,6 +103,10 @@ class Runner():
         self.guide = Guide(clip, self.pipe.tokenizer, device=device)
         self.generator = torch.Generator(device='cpu')     # E6: host generator
         self.eta = 0.0                                      # E5: never overwritten
+        # opt-in (always on under an SDE scheduler): step noise from the counter-based stream (noise.PhiloxNoise) keyed by
+        # the generator's seed, batch k of B samples at sample offset k * B -- k sequential batches see the noise of one
+        # batch of k * B
+        self.step_noise = False
         # the models and tokenizer tables are millions of long-lived objects: a full collection over them is a 50-100 ms
         # host stall between denoising loops (measured in bench.py's timed region)
         if freeze_gc:
@@ -119,7 +125,10 @@ class Runner():
         data-parallel axis (utils.py:90) -- and the grid of everything they produced.'''
         images: List[Any] = []
         extra = {'mask_image': mask_image} if mask_image is not None else {}
-        for _ in range(batches):
+        stochastic = self.step_noise or isinstance(self.pipe.scheduler, DPMSolverMultistepSDEScheduler)
+        for k in range(batches):
+            if stochastic:
+                self.pipe.step_noise = PhiloxNoise(self.generator.initial_seed(), sample_offset=k * guide.batch_size)
             result = self.pipe(guide=guide, init_image=init_image, init_size=init_size, strength=strength,
                                generator=self.generator, eta=self.eta, debug=debug, **extra)
             images += list(result['sample'])

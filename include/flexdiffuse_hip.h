@@ -492,6 +492,34 @@ int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, const float* z0
 int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1, const float* z0,
                               const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
                               float p, float q, float a, float w0, float w1, float k1, float k2, void* stream);
+/* Stochastic sampling on the device loop (additive; FD_ABI_VERSION stays 12): the step noise the reference's
+ * scheduler draws when `eta` is forwarded to it (pipeline/flex.py:247-251) comes from a counter-based normal stream
+ * generated inside the step kernel, never from a tensor.  Value z of flat element i of a launch:
+ *   key = (seed & 0xffffffff, seed >> 32) ;  sample = sample_offset + i / per ;  j = i % per
+ *   (w0, w1, w2, w3) = Philox4x32-10(counter = (j >> 2, sample, draw, stream), key)      (Salmon et al. 2011)
+ *   (wa, wb) = (w0, w1) for j % 4 in {0, 1}, (w2, w3) for j % 4 in {2, 3}
+ *   u = ((wa >> 8) + 1) 2^-24 ;  f = (wb >> 8) 2^-23 ;  r = sqrt(-2 log u) ;  z = r cospi(f) (j even) | r sinpi(f) (j odd)
+ * in fp32 (u, f exact; log, sincospi the accurate library functions; the products and the root separately rounded), so
+ * |z| < 5.77.  `per` is the number of elements of one sample (C * HW of the real latent) whatever (B, C) view the call
+ * uses; it must divide B * C * HW; sample_offset >= 0 is the global index of the call's first sample (a rank's or a
+ * batch's offset), draw >= 0 the step's index in the scheduler's timestep list; stream 0 is the step noise, stream 1 the
+ * stand-alone fill.  A value does not depend on the vector width, the batch split or the view.
+ * fd_philox_normal_f32: out[0..n) = z (n need not be a multiple of per; any alignment). */
+int fd_philox_normal_f32(float* out, int64_t n, int per, uint64_t seed, int64_t sample_offset, int draw, int noise_stream,
+                         void* stream);
+/* fd_cfg_ddim_masked_step_f32's fused form with the mask trio optional (mask == NULL: z0, noise, k1, k2 ignored) and
+ * DDIM's eta > 0 term: x' = c3 x0 + c4 e ;  x' = x' + sigma z (skipped when sigma == 0: the bits of the entry points
+ * above) ;  then the blend.  c4 = sqrt(1 - a_prev - sigma^2) comes from the host.  eps_nhwc must not be NULL. */
+int fd_cfg_ddim_noise_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise, const float* mask,
+                               int B, int C, int HW, int ld, int cfg, float guidance, float c1, float c2, float c3,
+                               float c4, int v_prediction, float k1, float k2, float sigma, uint64_t seed,
+                               int64_t sample_offset, int per, int draw, void* stream);
+/* fd_cfg_multistep_step_f32 plus the SDE-DPM-Solver++ term: ... x' = a x + w0 m0 (+ w1 m1) ;  x' = x' + sn z (skipped
+ * when sn == 0) ;  m0_out holds m0 ;  then the blend. */
+int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1, const float* z0,
+                                    const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
+                                    float guidance, float p, float q, float a, float w0, float w1, float k1, float k2,
+                                    float sn, uint64_t seed, int64_t sample_offset, int per, int draw, void* stream);
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
