@@ -10,7 +10,11 @@ context in rep-major order [uncond]*B [bg]*B [e_1]*B ...) and soft entity masks 
 blend * mean of the mask's 8x8 pixel cell per latent cell).  Those requests blend, combine and (in
 FlexPipeline's device loop) take the DDIM step in one launch, fd_composite_step_f32; batch 1 without
 masks keeps the per-entity fd_region_blend_f32 chain.  The style-blend embedding the reference
-computes at composition/guide.py:114-121 is dead code there and is not evaluated here.
+computes at composition/guide.py:114-121 is dead code there and is not evaluated here -- unless the
+caller opts in with `style_linear=(l0, l1)`: every prompt block E then gets the two keyframes
+E + omega (S_start - E) and E + omega (S_end - E), omega = linspace(l0, l1, tokens) per token (the reference's
+Linear style guidance), and step j runs on their blend at s_j = b0 + progress_j (b1 - b0), (b0, b1) the
+schema's `style_blend` -- a context schedule (ctx_schedule.py), on the batch-1 and on the device path.
 '''
 from __future__ import annotations
 
@@ -22,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from .. import hip, ops
+from ..ctx_schedule import ContextSchedule, step_weights
 from ..pipeline.guide import GuideBase
 from .schema import EntitySchema, Schema
 
@@ -69,7 +74,7 @@ def weight_maps(entities: Sequence[EntityEmbeds], H: int, W: int) -> torch.Tenso
 
 class CompositeGuide(GuideBase):
     def __init__(self, encoder, unet, guidance: float, schema: Schema, steps: int,
-                 batch_size: int = 1):
+                 batch_size: int = 1, style_linear: Optional[Tuple[float, float]] = None, mode: str = 'lerp'):
         GuideBase.__init__(self, encoder, unet, guidance, steps)
         if int(batch_size) < 1:
             raise ValueError(f'batch_size must be >= 1, got {batch_size}')
@@ -89,9 +94,29 @@ class CompositeGuide(GuideBase):
         # built once, rep-major: [uncond]*B, [bg]*B, [e_1]*B ... -- for B = 1 the reference's [uncond, bg, e_1, ...]
         self.embed_tensor = torch.cat([r.float().expand(B, -1, -1) for r in rows]).contiguous()
         self._wmaps = {}
+        # opt-in style blend (None: the reference-pinned behaviour above -- the style prompts are encoded nowhere)
+        self.context: Optional[ContextSchedule] = None
+        if style_linear is not None:
+            l0, l1 = (float(v) for v in style_linear)
+            first = 1 if self.classifier_free_guidance else 0
+            L = self.embed_tensor.shape[1]
+            omega = torch.linspace(l0, l1, L, dtype=torch.float32, device=self.embed_tensor.device).view(1, L, 1)
+            keys = []
+            for prompt in (schema.style_start_prompt, schema.style_end_prompt):
+                style = encoder.prompt(prompt).float().to(self.embed_tensor.device)
+                key = self.embed_tensor.clone()
+                body = key[first * B:]
+                body += omega * (style - body)          # the unconditional block keeps its rows: equal in both keyframes
+                keys.append(key)
+            self.context = ContextSchedule(unet, keys, step_weights(steps, 2, schema.style_blend), mode)
 
     def stacked_embeds(self) -> torch.Tensor:
-        return self.embed_tensor
+        return self.embed_tensor if self.context is None else self.context.handle()
+
+    def at_step(self, j: int):
+        '''FlexPipeline calls this with the global step index before every step; nothing without `style_linear`.'''
+        if self.context is not None:
+            self.context.at_step(j)
 
     def weights(self, H: int, W: int) -> Optional[torch.Tensor]:
         '''Device fp32 [n][H][W] blend weights (None without entities), built once per latent size and kept: a
@@ -118,11 +143,11 @@ class CompositeGuide(GuideBase):
         if self.on_device:
             if B != self.batch_size:
                 raise ValueError(f'latents batch {B} != the guide\'s batch_size {self.batch_size}')
-            eps = self.unet.forward_nhwc(latents, step, self.embed_tensor, rep=E)
+            eps = self.unet.forward_nhwc(latents, step, self.stacked_embeds(), rep=E)
             out = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
             self.step(None, eps, eps_out=out)
             return out
-        eps = self.unet.forward_nhwc(latents, step, self.embed_tensor, rep=E)
+        eps = self.unet.forward_nhwc(latents, step, self.stacked_embeds(), rep=E)
         stack = ops.nhwc_to_nchw(eps, E, C, H, W)            # (E,C,H,W) fp32
         first = 1 if self.classifier_free_guidance else 0
         bg = stack[first]

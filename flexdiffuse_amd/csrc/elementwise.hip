@@ -408,6 +408,54 @@ extern "C" int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stre
     return FD_OK;
 }
 
+// ---- out = a + w (b - a) on fp16 buffers: the per-step blend of two cached context projections (UNet2DConditionModel.blend_context) ------
+// Per element: half_rn(fd_lerp(float(a), float(b), w)) -- three separately rounded fp32 operations, one rounding to half.  w == 0 stores
+// a's bits and w == 1 stores b's bits (a + 1 * (b - a) is not b in fp32 when |a| >> |b|).  a == b therefore gives a for every w (a zero of
+// either sign gives +0 when 0 != w != 1).  HBM-bound: 16-byte accesses (8 halves per lane) when the three bases allow it.
+__device__ __forceinline__ half_t fd_lerp_h(half_t a, half_t b, float w) {
+    return w == 0.f ? a : w == 1.f ? b : (half_t)fd_lerp((float)a, (float)b, w);
+}
+
+template <int V>   // halves per lane and trip: 8 (all three bases 16-byte aligned) or 1
+__global__ __launch_bounds__(256) void k_lerp_f16(const half_t* __restrict__ a, const half_t* __restrict__ b, half_t* __restrict__ out,
+                                                   size_t n, float w) {
+    const size_t nv = n / V;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < nv; e += (size_t)gridDim.x * blockDim.x) {
+        if constexpr (V == 8) {
+            const half8 av = *reinterpret_cast<const half8*>(a + e * 8), bv = *reinterpret_cast<const half8*>(b + e * 8);
+            half8 o;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) o[i] = fd_lerp_h(av[i], bv[i], w);
+            *reinterpret_cast<half8*>(out + e * 8) = o;
+        } else {
+            out[e] = fd_lerp_h(a[e], b[e], w);
+        }
+    }
+    if constexpr (V == 8) {     // the tail: fewer than 8 halves, one lane each
+        const size_t t = nv * 8 + (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+        if (t < n) out[t] = fd_lerp_h(a[t], b[t], w);
+    }
+}
+
+extern "C" int fd_lerp_f16(const void* a, const void* b, void* out, int64_t n, float w, void* stream) {
+    FD_PLAN(fd_lerp_f16(a, b, out, n, w, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(a && b && out && n > 0, FD_EINVAL, "fd_lerp_f16: args");
+    FD_CHECK_ARG(out != a && out != b, FD_EINVAL, "fd_lerp_f16: out may alias neither input");
+    const bool vec = ((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) % 16 == 0;
+    if (vec) {
+        const int blocks = fd_grid1d((size_t)n / 8 + 8, 2048);
+        hipLaunchKernelGGL(k_lerp_f16<8>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)a, (const half_t*)b, (half_t*)out,
+                           (size_t)n, w);
+    } else {
+        const int blocks = fd_grid1d((size_t)n, 2048);
+        hipLaunchKernelGGL(k_lerp_f16<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)a, (const half_t*)b, (half_t*)out,
+                           (size_t)n, w);
+    }
+    FD_CHECK_LAUNCH("k_lerp_f16");
+    return FD_OK;
+}
+
 // ---- rectangular blend of one latent tensor onto another (CompositeGuide, reference
 // composition/guide.py:86-98): dst[:, oy:oy+sh, ox:ox+sw] += blend * (src - dst) on NCHW fp32
 __global__ void k_region_blend(float* __restrict__ dst, const float* __restrict__ src, int C, int H,

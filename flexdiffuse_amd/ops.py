@@ -1029,3 +1029,14 @@ def cast_f32(x: torch.Tensor) -> torch.Tensor:
     out = _empty(x.shape, torch.float32, x)
     hip.call('fd_cast_f16_to_f32', x.data_ptr(), out.data_ptr(), x.numel(), hip.stream())
     return out
+
+
+def lerp_f16(a: torch.Tensor, b: torch.Tensor, w: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    '''out = half(a + w (b - a)) elementwise on contiguous fp16 tensors (fd_lerp_f16: separately rounded fp32 operations; w == 0 / 1 copy
+    a / b bit for bit).  `out` may alias neither input.'''
+    assert a.dtype == b.dtype == torch.float16 and a.shape == b.shape and a.is_contiguous() and b.is_contiguous()
+    if out is None:
+        out = _empty(a.shape, torch.float16, a)
+    assert out.dtype == torch.float16 and out.shape == a.shape and out.is_contiguous()
+    hip.call('fd_lerp_f16', a.data_ptr(), b.data_ptr(), out.data_ptr(), a.numel(), float(w), hip.stream())
+    return out

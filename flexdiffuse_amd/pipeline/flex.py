@@ -23,6 +23,11 @@ region of the latents is put back on the re-noised init latents -- inside the fu
 (fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
 everywhere else.  Without a mask no path changes.
 
+Context schedules (beyond the reference; ctx_schedule.py): a guide with `at_step` (ScheduledGuide, a CompositeGuide with
+`style_linear=`) is told the global step index `t_start + i` at the top of every iteration, on every route, and makes the
+UNet's cached cross-attention projections those of the step's blend of its keyframe contexts -- one fd_lerp_f16 on the
+loop's stream before the graph / plan replay.  Guides without it run unchanged.
+
 Stochastic sampling (`pipe.step_noise`, a `noise.PhiloxNoise`; beyond the reference, which forwards `eta` to its scheduler,
 pipeline/flex.py:247-251): with it, SimpleGuide + DDIM + `eta > 0` stays on the device loop -- one fd_cfg_ddim_noise_step_f32 per
 step, the noise a counter-based stream generated inside the kernel -- and `DPMSolverMultistepSDEScheduler` runs the multistep
@@ -429,6 +434,10 @@ class FlexPipeline():
         rep = guide.rep if comp else 2 if cfg else 1
         vpred = fused and self.scheduler.config['prediction_type'] == 'v_prediction'
 
+        # a guide with a context schedule (ScheduledGuide, CompositeGuide(style_linear=)): told the GLOBAL step index at the top of
+        # every iteration, on every route; guides without `at_step` run as before
+        at_step = getattr(guide, 'at_step', None)
+
         def blend_known(x, i):
             # masked img2img behind any scheduler / guide: the blend-only launch on the step's result
             ops.cfg_ddim_masked_step(x, None, mask_z0, mask_n, mask_dev, B, C, H * W, k1=known[i][0], k2=known[i][1])
@@ -437,6 +446,9 @@ class FlexPipeline():
         # ~40 ms) and drains that queue, so collections wait until the images are decoded.
         with (_gc_paused() if self.pause_gc else contextlib.nullcontext()):
             for i, t in enumerate(self.progress_bar(self.scheduler.timesteps[t_start:])):
+                if at_step is not None:
+                    # a context schedule: the step's blend, issued eagerly on the loop's stream before the graph / plan replay reads it
+                    at_step(t_start + i)
                 if fused:
                     if debug:
                         # (a composite reads the request's time-bias table as the graph / plan do: bit-equal to them)

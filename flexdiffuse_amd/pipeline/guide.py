@@ -6,11 +6,12 @@ working.  `SimpleGuide` additionally exposes what FlexPipeline's fused device lo
 '''
 from __future__ import annotations
 
-from typing import List, Union
+from typing import List, Optional, Sequence, Union
 
 import torch
 
 from .. import ops
+from ..ctx_schedule import ContextSchedule, check_keyframes, step_weights
 
 
 class GuideBase():
@@ -66,3 +67,36 @@ class PromptGuide(SimpleGuide):
     def __init__(self, encoder, unet, guidance: float, steps: int, prompt: Union[str, List[str]]):
         SimpleGuide.__init__(self, encoder, unet, guidance, steps, encoder.prompt(prompt))
         self.prompt = prompt
+
+
+class ScheduledGuide(SimpleGuide):
+    '''SimpleGuide whose context moves over the steps (beyond the reference): `keyframes` are K >= 2 embeddings of one shape
+    (B, L, D) -- prompts, or a prompt and its image-guided form --, step j runs on key_k + w (key_{k+1} - key_k) with (k, w)
+    from ctx_schedule.step_weights(steps, K, schedule, positions).  `noise_pred` is SimpleGuide's own, so every fused and
+    planned route of FlexPipeline applies; the pipeline calls `at_step(t_start + i)` before each step.  mode='lerp': the
+    keyframes' cross-attention projections are cached and a step costs one fd_lerp_f16; mode='project' (or FD_CTX_LERP=0):
+    the blended context is reprojected every step.'''
+
+    def __init__(self, encoder, unet, guidance: float, steps: int, keyframes: Sequence[torch.Tensor],
+                 schedule: Sequence[float] = (0.0, 1.0), positions: Optional[Sequence[float]] = None, mode: str = 'lerp'):
+        check_keyframes(keyframes)
+        weights = step_weights(steps, len(keyframes), schedule, positions)
+        SimpleGuide.__init__(self, encoder, unet, guidance, steps, keyframes[0])
+        self.keyframes = list(keyframes)
+        B = self.batch_size
+        if self.classifier_free_guidance:       # [uncond]*B + keyframe, as SimpleGuide.stacked_embeds stacks its one context
+            un = self.uncond_embeds.float().expand(B, -1, -1)
+            stacked = [torch.cat([un, k.float()]).contiguous() for k in keyframes]
+        else:
+            stacked = [k.float().contiguous() for k in keyframes]
+        self.context = ContextSchedule(unet, stacked, weights, mode)
+
+    @property
+    def weights(self):
+        return self.context.weights
+
+    def at_step(self, j: int):
+        self.context.at_step(j)
+
+    def stacked_embeds(self) -> torch.Tensor:
+        return self.context.handle()

@@ -189,6 +189,7 @@ class UNet2DConditionModel():
         self._attn_layers = [a for blk in self.down for a in blk['attn'] if a] + [self.mid_attn] + \
                             [a for blk in self.up for a in blk['attn'] if a]
         self._ctx_key = None
+        self._ctx_sched = None      # schedule mode (set_context_keyframes): arenas, handle, what the live arena holds
         # bumped whenever set_context REALLOCATES the cached K / V^T buffers (instead of rewriting
         # them in place): a captured HIP graph of the forward holds the old addresses and must not
         # be replayed after that (FlexPipeline keys its graph cache on this counter)
@@ -241,6 +242,12 @@ class UNet2DConditionModel():
         if key == self._ctx_key:
             return
         hip.require_device(ctx)
+        if self._ctx_sched is not None:
+            # leaving schedule mode: the layers' buffers are views of the schedule's live arena -- drop them, so that this
+            # context gets buffers of its own (and ctx_generation moves: graphs / plans of the schedule read the arena)
+            self._ctx_sched = None
+            for a in self._attn_layers:
+                a.ctx_kv, a.ctx_img = None, None
         Be, L, D = ctx.shape
         c16 = ops.cast_f16(ctx.reshape(Be * L, D)) if ctx.dtype != torch.float16 \
             else ctx.reshape(Be * L, D).contiguous()
@@ -266,6 +273,96 @@ class UNet2DConditionModel():
             self.ctx_generation += 1
         self._ctx_key = key
         self._ctx_ref = ctx  # keep the tensor alive so its data_ptr cannot be recycled
+
+    # ---- context schedules (per-step blends of cached projections) ------------------------------
+    def _ctx_layout(self, Be: int, L: int):
+        '''(halves per arena, per layer (K offset, V^T offset, image offsets or None, image bytes)) of one context's
+        projections laid out back to back, every buffer at a 16-byte aligned offset (8 halves).'''
+        ldv = (L + 7) // 8 * 8
+        up = lambda n: (n + 7) // 8 * 8      # noqa: E731
+        off, slots = 0, []
+        for a in self._attn_layers:
+            d = a.C // a.heads
+            ok, off = off, off + up(Be * L * a.C)
+            ov, off = off, off + up(Be * a.C * ldv)
+            oi, nb = None, 0
+            if a.ln_fold and a.q_pre and ops.xattn_supported(a.heads, d, L, ops.xattn_row_tile(d)):
+                nb = hip.lib().fd_xattn_image_bytes(a.heads, d)
+                oi = (off, off + up(Be * nb // 2))
+                off = oi[1] + up(Be * nb // 2)
+            slots.append((ok, ov, oi, nb))
+        return off, slots
+
+    @staticmethod
+    def _ctx_views(arena: torch.Tensor, slot, Be: int, L: int, C: int):
+        '''((K, V^T, L), (K image, V^T image) or None) of one layer as views of `arena`.'''
+        ok, ov, oi, nb = slot
+        ldv = (L + 7) // 8 * 8
+        kv = (arena[ok:ok + Be * L * C].view(Be * L, C), arena[ov:ov + Be * C * ldv].view(Be, C, ldv), L)
+        img = None if oi is None else tuple(arena[o:o + Be * nb // 2].view(torch.uint8).view(Be, nb) for o in oi)
+        return kv, img
+
+    def set_context_keyframes(self, ctxs) -> torch.Tensor:
+        '''Schedule mode: project every keyframe context (same shape (Be, L, D), at least two) exactly as set_context does --
+        cast, K GEMM, V^T GEMM, the packed images where set_context packs -- each into ONE contiguous zero-initialised fp16
+        arena, and make every layer's cached K / V^T / images views of one more arena of the same layout, the LIVE context,
+        which blend_context fills.  Returns the handle: the tensor to pass to the forward as the context (it only names
+        the schedule; the forward does not reproject).  A later set_context(other) leaves schedule mode.'''
+        from .ctx_schedule import check_keyframes
+        Be, L, D = check_keyframes(ctxs)
+        key = tuple((c.data_ptr(), c._version, tuple(c.shape)) for c in ctxs)
+        sch = self._ctx_sched
+        if sch is not None and sch['key'] == key:
+            return sch['handle']
+        hip.require_device(*ctxs)
+        total, slots = self._ctx_layout(Be, L)
+        if sch is None or sch['shape'] != (len(ctxs), Be, L, D):
+            # (zeros: the pad columns of V^T and the gaps between buffers stay 0 in every arena, and 0 blends to 0)
+            arenas = [torch.zeros((total,), dtype=torch.float16, device=self.device) for _ in range(len(ctxs) + 1)]
+            sch = {'shape': (len(ctxs), Be, L, D), 'arenas': arenas,
+                   'handle': torch.zeros((Be, L, D), dtype=torch.float16, device=self.device)}
+            for a, slot in zip(self._attn_layers, slots):
+                a.ctx_kv, a.ctx_img = self._ctx_views(arenas[-1], slot, Be, L, a.C)
+            self.ctx_generation += 1
+        ldv = (L + 7) // 8 * 8
+        for ctx, arena in zip(ctxs, sch['arenas']):
+            c16 = ops.cast_f16(ctx.reshape(Be * L, D)) if ctx.dtype != torch.float16 else ctx.reshape(Be * L, D).contiguous()
+            for a, slot in zip(self._attn_layers, slots):
+                kv, img = self._ctx_views(arena, slot, Be, L, a.C)
+                ops.gemm(c16, a.k2, out=kv[0])
+                ops.gemm_vt(c16, a.v2, Be, L, ldv, out=kv[1])
+                if img is not None:
+                    ops.xattn_pack_kv(kv[0], kv[1], Be, L, a.heads, a.C // a.heads, out=img)
+        sch['key'], sch['refs'], sch['live'] = key, list(ctxs), None
+        self._ctx_sched = sch
+        h = sch['handle']
+        self._ctx_key, self._ctx_ref = (h.data_ptr(), h._version, tuple(h.shape)), h
+        self.blend_context(0, 0.0)
+        return h
+
+    def context_buffers(self, i: int = -1):
+        '''Per cross-attention layer ((K, V^T, L), (K image, V^T image) or None) of keyframe `i` of the schedule; -1: the
+        live context the forward reads.'''
+        sch = self._ctx_sched
+        if sch is None:
+            raise RuntimeError('context_buffers needs set_context_keyframes first (the UNet is not in schedule mode)')
+        _, Be, L, _ = sch['shape']
+        slots = self._ctx_layout(Be, L)[1]
+        return [self._ctx_views(sch['arenas'][i], slot, Be, L, a.C) for a, slot in zip(self._attn_layers, slots)]
+
+    def blend_context(self, k: int, w: float):
+        '''live = key_k + w (key_{k+1} - key_k) over the whole arena: one fd_lerp_f16 on the current stream (K, V^T and the
+        packed images of every layer at once); nothing when the live arena already holds (k, w).'''
+        sch = self._ctx_sched
+        if sch is None:
+            raise RuntimeError('blend_context needs set_context_keyframes first (the UNet is not in schedule mode)')
+        arenas = sch['arenas']
+        if not 0 <= k < len(arenas) - 2:
+            raise ValueError(f'segment {k} of {len(arenas) - 1} keyframes')
+        if sch['live'] == (k, float(w)):
+            return
+        ops.lerp_f16(arenas[k], arenas[k + 1], float(w), out=arenas[-1])
+        sch['live'] = (k, float(w))
 
     # ---- blocks -----------------------------------------------------------------------------
     @staticmethod

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import dataclasses
 import gc
+import inspect
 import math
 import os
 from typing import Any, Dict, List, Optional, Sequence, Tuple
@@ -27,7 +28,7 @@ from .encode.clip import CLIPEncoder
 from .guidance import Guide
 from .composition import CompositeGuide, EntitySchema, Schema
 from .noise import PhiloxNoise
-from .pipeline.guide import GuideBase, SimpleGuide
+from .pipeline.guide import GuideBase, ScheduledGuide, SimpleGuide
 from .scheduler import DPMSolverMultistepSDEScheduler
 
 MAX_SEED = 2147483647          # the reference clamps seeds to int32 (utils.py:22)
@@ -35,6 +36,9 @@ MAX_SEED = 2147483647          # the reference clamps seeds to int32 (utils.py:2
 # the keyword arguments `gen` forwards untouched to `Guide.embeds` (utils.py:151-162)
 _EMBEDS_KEYS = ('mapping_concepts', 'guide_threshold_mult', 'guide_threshold_floor', 'guide_clustered',
                 'guide_linear', 'guide_max_guidance', 'guide_header_max', 'guide_mode', 'guide_reuse')
+
+
+_SAME = object()              # `gen_scheduled(end_guide=)`: the same guide image as `guide`
 
 
 def image_grid(imgs: Sequence[Any]):
@@ -158,11 +162,33 @@ class Runner():
             mask_image=None):
         '''Same arguments and defaults as utils.py:114-133; returns (images, grid).  Beyond the
         reference: `mask_image` over `init_image` (1 = repaint, 0 = keep; `FlexPipeline.__call__`).'''
-        given = locals()
-        self._set_seed(seed)
-        embeds = self.guide.embeds(prompt=prompt, guide=guide, **{k: given[k] for k in _EMBEDS_KEYS})
-        return self._run(samples, SimpleGuide(self.encoder, self.pipe.unet, guidance_scale, steps, embeds),
-                         init_image, init_size, strength, debug, **({'mask_image': mask_image} if mask_image is not None else {}))
+        return self._gen(locals())
+
+    def gen_scheduled(self, prompt='', *, end_prompt=None, end_guide=_SAME, schedule: Sequence[float] = (0.0, 1.0), **gen_args):
+        '''`gen` whose context moves over the steps (beyond the reference; `ScheduledGuide`): a second keyframe is embedded
+        from `end_prompt` (default: `prompt`) and `end_guide` (default: the same guide image as `guide`) with the same
+        guidance parameters, and the request goes from the first keyframe to the second by `schedule` -- a (first, last)
+        pair of blend weights or one weight per step: prompt travel, or a guide image faded in or out.  Every other
+        argument is `gen`'s, by keyword (`gen` itself keeps the reference's signature).'''
+        given = inspect.signature(Runner.gen).bind(self, prompt, **gen_args)
+        given.apply_defaults()
+        return self._gen(dict(given.arguments), (end_prompt, end_guide, schedule))
+
+    def _gen(self, given: Dict[str, Any], travel=None):
+        self._set_seed(given['seed'])
+        params = {k: given[k] for k in _EMBEDS_KEYS}
+        unet, scale, steps = self.pipe.unet, given['guidance_scale'], given['steps']
+        embeds = self.guide.embeds(prompt=given['prompt'], guide=given['guide'], **params)
+        if travel is None:
+            g = SimpleGuide(self.encoder, unet, scale, steps, embeds)
+        else:
+            end_prompt, end_guide, schedule = travel
+            end = self.guide.embeds(prompt=given['prompt'] if end_prompt is None else end_prompt,
+                                    guide=given['guide'] if end_guide is _SAME else end_guide, **params)
+            g = ScheduledGuide(self.encoder, unet, scale, steps, [embeds, end], schedule)
+        mask_image = given['mask_image']
+        return self._run(given['samples'], g, given['init_image'], given['init_size'], given['strength'], given['debug'],
+                         **({'mask_image': mask_image} if mask_image is not None else {}))
 
     def compose(self,
                 bg_prompt: str = '',
@@ -188,7 +214,27 @@ class Runner():
         Beyond the reference: `batch_size` samples per pipeline call (one UNet forward; `batches *
         batch_size` images in all) and `masks`, aligned with the table rows (None: the rectangle),
         each an EntitySchema mask over its box; `mask_image` over `init_image` (1 = repaint, 0 = keep:
-        masked img2img, `FlexPipeline.__call__`).'''
+        masked img2img, `FlexPipeline.__call__`).  The style arguments are stored in the schema and, as in the
+        reference, not applied; `compose_styled` applies them.'''
+        return self._compose(locals())
+
+    def compose_styled(self, bg_prompt: str = '', entities_df: Sequence[Sequence[Any]] = (), start_style: str = '',
+                       end_style: str = '', style_blend: Tuple[float, float] = (0.0, 1.0), *,
+                       style_linear: Tuple[float, float] = (0.0, 0.5), **compose_args):
+        '''`compose` with the style blend the reference's composer asks for and drops (beyond the reference;
+        `CompositeGuide(style_linear=)`): `start_style` / `end_style` pull every prompt by linspace(*style_linear) per
+        token and the request moves from the start style to the end style by `style_blend`.  Every other argument is
+        `compose`'s, by keyword (`compose` itself keeps the reference's signature).'''
+        given = inspect.signature(Runner.compose).bind(self, bg_prompt, entities_df, start_style, end_style, style_blend,
+                                                       **compose_args)
+        given.apply_defaults()
+        return self._compose(dict(given.arguments), style_linear)
+
+    def _compose(self, given: Dict[str, Any], style_linear=None):
+        (bg_prompt, entities_df, start_style, end_style, style_blend, init_image, batches, strength, steps, guidance_scale,
+         init_size, seed, debug, batch_size, masks, mask_image) = (given[k] for k in (
+             'bg_prompt', 'entities_df', 'start_style', 'end_style', 'style_blend', 'init_image', 'batches', 'strength',
+             'steps', 'guidance_scale', 'init_size', 'seed', 'debug', 'batch_size', 'masks', 'mask_image'))
         self._set_seed(seed)
         table = getattr(entities_df, '_values', entities_df)
         parsed = [entity_from_row(row) for row in table]
@@ -200,6 +246,8 @@ class Runner():
         entities = [e for e in parsed if e is not None and e.prompt]
         self.last_schema = Schema(bg_prompt, start_style, end_style, style_blend, entities)
         extra = {'batch_size': batch_size} if batch_size != 1 else {}
+        if style_linear is not None:
+            extra['style_linear'] = style_linear
         guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps, **extra)
         # (only when given: a subclass's `_run` with the reference's six arguments keeps working)
         return self._run(batches, guide, init_image, init_size, strength, debug,

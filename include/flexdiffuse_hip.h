@@ -520,6 +520,13 @@ int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_o
                                     const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
                                     float guidance, float p, float q, float a, float w0, float w1, float k1, float k2,
                                     float sn, uint64_t seed, int64_t sample_offset, int per, int draw, void* stream);
+/* Context schedules (additive; FD_ABI_VERSION stays 12): out[i] = half_rn(a[i] + w * (b[i] - a[i])) on contiguous fp16 buffers of n
+ * elements -- the subtraction, the product and the sum three separately rounded fp32 operations (no FMA), one rounding to half.
+ * w == 0 stores a's bits, w == 1 stores b's bits; a[i] == b[i] gives a[i] for every w (a zero of either sign: +0 unless w is 0 or 1).
+ * The cross-attention projections are linear, so the K, V^T and packed images of a blended context are this blend of the
+ * cached projections of its keyframes (UNet2DConditionModel.blend_context).  16-byte accesses when a, b and out are all 16-byte
+ * aligned, a scalar kernel otherwise; out may alias neither input (FD_EINVAL, as are NULL pointers and n <= 0). */
+int fd_lerp_f16(const void* a, const void* b, void* out, int64_t n, float w, void* stream);
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
