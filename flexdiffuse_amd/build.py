@@ -177,7 +177,7 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
     reference passes into its pipeline (utils.py:70: `sd.scheduler` -- PNDM/PLMS for CompVis/stable-diffusion-v1-4, so a
     50-step request is 51 UNet evaluations).  `_class_name` -> PNDMScheduler / LMSDiscreteScheduler / DDIMScheduler /
     DPMSolverMultistepScheduler with the betas, `skip_prk_steps`, `steps_offset`, `set_alpha_to_one`, `clip_sample`,
-    `solver_order`, `lower_order_final` of the file.  None when the checkpoint has
+    `solver_order`, `lower_order_final`, `rescale_betas_zero_snr` and (DDIM) `timestep_spacing` of the file.  None when the checkpoint has
     no scheduler folder; NotImplementedError for a class this package does not provide (never a silent substitute).'''
     import json
     import os
@@ -197,6 +197,12 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
         # silently wrong image
         raise NotImplementedError(f'{path}: {name} with prediction_type {ptype!r} is not provided (epsilon only); pass '
                                   'scheduler=DDIMScheduler(prediction_type=...) to choose one explicitly')
+    zero_snr = bool(cfg.get('rescale_betas_zero_snr', False))
+    if zero_snr and ptype != 'v_prediction':
+        # at the last timestep of that table alphas_cumprod is 0: an epsilon model's x0 divides by it (PNDM and K-LMS are
+        # epsilon only, so the key is never dropped silently for them either)
+        raise NotImplementedError(f'{path}: rescale_betas_zero_snr=True with prediction_type {ptype!r} is not provided '
+                                  '(zero terminal SNR needs prediction_type \'v_prediction\')')
     if name == 'PNDMScheduler':
         extra = {'skip_prk_steps': cfg.get('skip_prk_steps', False), 'steps_offset': cfg.get('steps_offset', 0)}
         return PNDMScheduler(**common, **extra)
@@ -205,7 +211,12 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
     if name == 'DDIMScheduler':
         extra = {'clip_sample': cfg.get('clip_sample', True), 'set_alpha_to_one': cfg.get('set_alpha_to_one', True),
                  'steps_offset': cfg.get('steps_offset', 0)}
-        return DDIMScheduler(**common, **extra, prediction_type=ptype)
+        spacing = cfg.get('timestep_spacing', 'leading')
+        if spacing not in ('leading', 'trailing'):
+            raise NotImplementedError(f'{path}: DDIMScheduler with timestep_spacing={spacing!r} is not provided (only '
+                                      '\'leading\', \'trailing\'); pass scheduler= to choose one explicitly')
+        return DDIMScheduler(**common, **extra, prediction_type=ptype, timestep_spacing=spacing,
+                             rescale_betas_zero_snr=zero_snr)
     if name == 'DPMSolverMultistepScheduler':
         # DPM-Solver++ (2M), midpoint form, on the linspace grid is what is provided; every other variant the file can ask
         # for is refused by the key that asks for it
@@ -216,7 +227,8 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
                 raise NotImplementedError(f'{path}: DPMSolverMultistepScheduler with {key}={cfg[key]!r} is not provided '
                                           f'(only {", ".join(repr(v) for v in ok)}); pass scheduler= to choose one explicitly')
         return DPMSolverMultistepScheduler(**common, solver_order=cfg.get('solver_order', 2), prediction_type=ptype,
-                                           lower_order_final=cfg.get('lower_order_final', True))
+                                           lower_order_final=cfg.get('lower_order_final', True),
+                                           rescale_betas_zero_snr=zero_snr)
     raise NotImplementedError(f'{path}: scheduler class {name!r} is not provided (PNDMScheduler, LMSDiscreteScheduler, '
                               'DDIMScheduler, DPMSolverMultistepScheduler are); pass scheduler= to choose one explicitly')
 

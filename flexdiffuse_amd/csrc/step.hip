@@ -7,8 +7,11 @@
 //   fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32   the stochastic forms (DDIM eta > 0, SDE-DPM-Solver++):
 //                                the same steps plus x' += sn z, z the counter-based normal stream of philox.h generated
 //                                in the kernel; fd_philox_normal_f32 writes that stream out on its own
+//   fd_cfg_rescale_ddim_step_f32, fd_cfg_rescale_multistep_step_f32   guidance rescale: all of the above with the guided e
+//                                of each sample multiplied by a factor from two of its standard deviations, computed in the
+//                                step's own launch (k_latent_step_rescale, one workgroup per sample, the same per-group body)
 // Per element, in this order, every operation a separately rounded fp32 one (latent_step.h; no FMA):
-//   e = u + g (t - u) (cfg; otherwise the one eps row) -> eps_out ;  the update ;  + sn z (sn != 0) ;  -> m0_out ;
+//   e = u + g (t - u) (cfg; otherwise the one eps row) ;  e = f_b e (rescaled forms) -> eps_out ;  the update ;  + sn z (sn != 0) ;  -> m0_out ;
 //   the blend (mask) ;  -> x
 // so the entry points are bit-equal to each other wherever they overlap (an all-ones mask is the plain step, an
 // all-zeros mask is fd_axpby_f32(z0, n, k1, k2), the fused form is the plain step + the blend-only form, DPM-Solver++
@@ -35,6 +38,55 @@ struct FdStepArgs {
 // One thread owns V consecutive pixels of one (b, c) plane.  V = 4: HW % 4 == 0 and 16-byte bases, so a group never
 // straddles a plane and every NCHW tensor moves as float4; the NHWC eps rows (stride ld) are read per pixel.  NOISE (with
 // V = 4: per % 4 == 0 too, so a group is one Philox block): x' += sn z between the update and the blend.
+// fd_step_group is the whole step of the group whose first pixel is NCHW element e = (b, c, p), the one body of
+// k_latent_step and k_latent_step_rescale; RESCALE: the guided output is multiplied by the sample's factor f between the CFG
+// combine and everything after it.
+template <int V, int UPDATE, bool NOISE, bool RESCALE>
+__device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int b, int c, int p, bool use_x, float f) {
+    float xv[V], ev[V], hv[V], zv[V], nv[V], mv[V];
+    if (use_x) fd_ldv<V>(a.x + e, xv);
+    if (UPDATE == FD_STEP_MULTISTEP && a.m1) fd_ldv<V>(a.m1 + e, hv);
+    if (a.mask) {
+        fd_ldv<V>(a.z0 + e, zv);
+        fd_ldv<V>(a.nz + e, nv);
+        fd_ldv<V>(a.mask + p, mv);
+    }
+    if (a.eps) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const size_t row = ((size_t)b * a.HW + p + j) * a.ld + c;
+            ev[j] = a.cfg ? fd_cfg_mix(a.eps[row], a.eps[row + (size_t)a.B * a.HW * a.ld], a.g) : a.eps[row];
+            if constexpr (RESCALE) ev[j] = __fmul_rn(f, ev[j]);
+        }
+        if (a.eps_out) fd_stv<V>(a.eps_out + e, ev);
+    }
+    if constexpr (UPDATE == FD_STEP_DDIM) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) xv[j] = fd_ddim_update(xv[j], ev[j], a.co[0], a.co[1], a.co[2], a.co[3], a.vpred);
+    } else if constexpr (UPDATE == FD_STEP_MULTISTEP) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float d0 = __fadd_rn(__fmul_rn(a.co[0], xv[j]), __fmul_rn(a.co[1], ev[j]));
+            float xn = __fadd_rn(__fmul_rn(a.co[2], xv[j]), __fmul_rn(a.co[3], d0));
+            if (a.m1) xn = __fadd_rn(xn, __fmul_rn(a.co[4], hv[j]));
+            ev[j] = d0;
+            xv[j] = xn;
+        }
+        fd_stv<V>(a.m0_out + e, ev);
+    }
+    if constexpr (NOISE) {
+        float sv[V];
+        fd_noise_normals<V>(a.nz_addr, e, sv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) xv[j] = __fadd_rn(xv[j], __fmul_rn(a.sn, sv[j]));
+    }
+    if (a.mask) {
+#pragma unroll
+        for (int j = 0; j < V; ++j) xv[j] = fd_known_blend(xv[j], zv[j], nv[j], mv[j], a.k1, a.k2);
+    }
+    if (use_x) fd_stv<V>(a.x + e, xv);
+}
+
 template <int V, int UPDATE, bool NOISE>
 __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
     const size_t groups = (size_t)a.B * a.C * a.HW / V;
@@ -45,47 +97,70 @@ __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
         const size_t r = e / a.HW;
         const int c = r % a.C;
         const int b = r / a.C;
-        float xv[V], ev[V], hv[V], zv[V], nv[V], mv[V];
-        if (use_x) fd_ldv<V>(a.x + e, xv);
-        if (UPDATE == FD_STEP_MULTISTEP && a.m1) fd_ldv<V>(a.m1 + e, hv);
-        if (a.mask) {
-            fd_ldv<V>(a.z0 + e, zv);
-            fd_ldv<V>(a.nz + e, nv);
-            fd_ldv<V>(a.mask + p, mv);
-        }
-        if (a.eps) {
+        fd_step_group<V, UPDATE, NOISE, false>(a, e, b, c, p, use_x, 1.f);
+    }
+}
+
+// ---- guidance rescale (Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", sec. 3.4) ----
+// The guided output e of sample b is multiplied by f_b = phi sqrt(M2(t) / M2(e)) + (1 - phi), t the conditional rows,
+// M2(v) = sum v^2 - (sum v)^2 / n over the sample's n = C HW real elements (the n - 1 of the two unbiased deviations
+// cancels): diffusers' rescale_noise_cfg.  One workgroup of FD_RESCALE_THREADS per sample, so the statistics need neither
+// atomics nor a workspace nor a second launch.  Phase 1: every thread walks its groups of the sample in stride order and
+// accumulates the four sums in fp64 (the square of an fp32 value is exact there); a fixed butterfly per wave, the wave
+// partials through LDS, summed in wave order by thread 0, which rounds f_b to fp32 once.  Phase 2: fd_step_group with the
+// multiply, on eps rows that are cache-hot.  The order of every sum is fixed by the launch shape alone: same bits on every
+// run and on every loop mode.  phi == 0 or M2(e) <= 0: f_b = 1, the bits of k_latent_step.
+enum { FD_RESCALE_THREADS = 1024, FD_RESCALE_WAVES = FD_RESCALE_THREADS / 64 };
+
+template <int V, int UPDATE, bool NOISE>
+__global__ __launch_bounds__(FD_RESCALE_THREADS) void k_latent_step_rescale(const FdStepArgs a, const float phi,
+                                                                            float* __restrict__ scale_out) {
+    __shared__ double part[FD_RESCALE_WAVES][4];
+    __shared__ float f_s;
+    const int b = blockIdx.x;
+    const unsigned n = (unsigned)a.C * a.HW, per = n / V;            // elements and groups of one sample (n < 2^31: the launcher)
+    const size_t half = (size_t)a.B * a.HW * a.ld;                   // the conditional rows follow the unconditional ones
+    double s[4] = {0.0, 0.0, 0.0, 0.0};                              // sum t, sum t^2, sum e, sum e^2
+    for (unsigned gi = threadIdx.x; gi < per; gi += FD_RESCALE_THREADS) {
+        const unsigned q = gi * V;                                   // element inside the sample: (c, p), 32-bit arithmetic
+        const int p = q % (unsigned)a.HW;
+        const int c = q / (unsigned)a.HW;
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const size_t row = ((size_t)b * a.HW + p + j) * a.ld + c;
-                ev[j] = a.cfg ? fd_cfg_mix(a.eps[row], a.eps[row + (size_t)a.B * a.HW * a.ld], a.g) : a.eps[row];
-            }
-            if (a.eps_out) fd_stv<V>(a.eps_out + e, ev);
+        for (int j = 0; j < V; ++j) {
+            const size_t row = ((size_t)b * a.HW + p + j) * a.ld + c;
+            const float tf = a.eps[row + half];
+            const double t = tf, e = fd_cfg_mix(a.eps[row], tf, a.g);
+            s[0] += t;
+            s[1] += t * t;
+            s[2] += e;
+            s[3] += e * e;
         }
-        if constexpr (UPDATE == FD_STEP_DDIM) {
+    }
 #pragma unroll
-            for (int j = 0; j < V; ++j) xv[j] = fd_ddim_update(xv[j], ev[j], a.co[0], a.co[1], a.co[2], a.co[3], a.vpred);
-        } else if constexpr (UPDATE == FD_STEP_MULTISTEP) {
+    for (int k = 0; k < 4; ++k)
 #pragma unroll
-            for (int j = 0; j < V; ++j) {
-                const float d0 = __fadd_rn(__fmul_rn(a.co[0], xv[j]), __fmul_rn(a.co[1], ev[j]));
-                float xn = __fadd_rn(__fmul_rn(a.co[2], xv[j]), __fmul_rn(a.co[3], d0));
-                if (a.m1) xn = __fadd_rn(xn, __fmul_rn(a.co[4], hv[j]));
-                ev[j] = d0;
-                xv[j] = xn;
-            }
-            fd_stv<V>(a.m0_out + e, ev);
-        }
-        if constexpr (NOISE) {
-            float sv[V];
-            fd_noise_normals<V>(a.nz_addr, e, sv);
+        for (int off = 32; off > 0; off >>= 1) s[k] += __shfl_xor(s[k], off, 64);
+    if ((threadIdx.x & 63) == 0)
 #pragma unroll
-            for (int j = 0; j < V; ++j) xv[j] = __fadd_rn(xv[j], __fmul_rn(a.sn, sv[j]));
-        }
-        if (a.mask) {
+        for (int k = 0; k < 4; ++k) part[threadIdx.x >> 6][k] = s[k];
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double tot[4] = {0.0, 0.0, 0.0, 0.0};
+        for (int w = 0; w < FD_RESCALE_WAVES; ++w)
 #pragma unroll
-            for (int j = 0; j < V; ++j) xv[j] = fd_known_blend(xv[j], zv[j], nv[j], mv[j], a.k1, a.k2);
-        }
-        if (use_x) fd_stv<V>(a.x + e, xv);
+            for (int k = 0; k < 4; ++k) tot[k] += part[w][k];
+        const double m2t = tot[1] - tot[0] * tot[0] / (double)n, m2e = tot[3] - tot[2] * tot[2] / (double)n;
+        float f = 1.f;
+        if (phi != 0.f && m2e > 0.0) f = (float)((double)phi * sqrt(fmax(m2t, 0.0) / m2e) + (1.0 - (double)phi));
+        f_s = f;
+        if (scale_out) scale_out[b] = f;
+    }
+    __syncthreads();
+    const float f = f_s;
+    const bool use_x = UPDATE != FD_STEP_NONE || a.mask;
+    for (unsigned gi = threadIdx.x; gi < per; gi += FD_RESCALE_THREADS) {
+        const unsigned q = gi * V;
+        fd_step_group<V, UPDATE, NOISE, true>(a, (size_t)b * n + q, b, q / (unsigned)a.HW, q % (unsigned)a.HW, use_x, f);
     }
 }
 
@@ -207,6 +282,87 @@ extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, 
                                  (unsigned long long)B * C * HW, &s.nz_addr);
     if (rc != FD_OK) return rc;
     return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+}
+
+// ---- the rescaled forms ----------------------------------------------------------------------------------------------
+// k_latent_step's vector rule; one workgroup per sample
+static int fd_latent_step_rescale(int update, const FdStepArgs& a, float phi, float* scale_out, void* stream) {
+    uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
+    if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
+    if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
+    const int noise = update != FD_STEP_NONE && a.sn != 0.f;
+    const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
+    static void (*const kernels[2][2][3])(const FdStepArgs, float, float*) = {
+        {{k_latent_step_rescale<1, FD_STEP_NONE, false>, k_latent_step_rescale<1, FD_STEP_DDIM, false>,
+          k_latent_step_rescale<1, FD_STEP_MULTISTEP, false>},
+         {k_latent_step_rescale<4, FD_STEP_NONE, false>, k_latent_step_rescale<4, FD_STEP_DDIM, false>,
+          k_latent_step_rescale<4, FD_STEP_MULTISTEP, false>}},
+        {{nullptr, k_latent_step_rescale<1, FD_STEP_DDIM, true>, k_latent_step_rescale<1, FD_STEP_MULTISTEP, true>},
+         {nullptr, k_latent_step_rescale<4, FD_STEP_DDIM, true>, k_latent_step_rescale<4, FD_STEP_MULTISTEP, true>}}};
+    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(a.B), dim3(FD_RESCALE_THREADS), 0, (hipStream_t)stream, a, phi,
+                       scale_out);
+    FD_CHECK_LAUNCH("k_latent_step_rescale");
+    return FD_OK;
+}
+
+// the checks the two rescaled entry points share (the siblings' own, plus the factor's range and the sample size)
+static int fd_rescale_args(const char* who, const float* eps_nhwc, int B, int C, int HW, int ld, float rescale) {
+    FD_CHECK_ARG(eps_nhwc, FD_EINVAL, "%s: eps_nhwc is null", who);
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
+    FD_CHECK_ARG((unsigned long long)C * HW <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * HW past 2^31", who);
+    FD_CHECK_ARG(rescale >= 0.f && rescale <= 1.f, FD_EINVAL, "%s: rescale %g is outside [0, 1]", who, (double)rescale);
+    return FD_OK;
+}
+
+extern "C" int fd_cfg_rescale_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* scale_out,
+                                            const float* z0, const float* noise, const float* mask, int B, int C, int HW,
+                                            int ld, float guidance, float rescale, float c1, float c2, float c3, float c4,
+                                            int v_prediction, int do_step, float k1, float k2, float sigma, uint64_t seed,
+                                            int64_t sample_offset, int draw, void* stream) {
+    FD_PLAN(fd_cfg_rescale_ddim_step_f32(x, eps_nhwc, eps_out, scale_out, z0, noise, mask, B, C, HW, ld, guidance, rescale,
+                                         c1, c2, c3, c4, v_prediction, do_step, k1, k2, sigma, seed, sample_offset, draw,
+                                         fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    const int rc = fd_rescale_args("fd_cfg_rescale_ddim_step_f32", eps_nhwc, B, C, HW, ld, rescale);
+    if (rc != FD_OK) return rc;
+    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: x is null");
+    FD_CHECK_ARG(do_step || (eps_out && !mask && sigma == 0.f), FD_EINVAL,
+                 "fd_cfg_rescale_ddim_step_f32: the combine-only form needs eps_out and takes neither mask nor sigma");
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: mask without z0 / noise (null)");
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: z0 / noise alias the latents");
+    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: eps_out aliases the latents");
+    FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, 1, v_prediction,
+                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, do_step ? sigma : 0.f, {}};
+    if (a.sn != 0.f) {
+        const int rn = fd_noise_addr("fd_cfg_rescale_ddim_step_f32", seed, sample_offset, C * HW, draw, 0,
+                                     (unsigned long long)B * C * HW, &a.nz_addr);
+        if (rn != FD_OK) return rn;
+    }
+    return fd_latent_step_rescale(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, rescale, scale_out, stream);
+}
+
+extern "C" int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
+                                                 float* scale_out, const float* z0, const float* noise, const float* mask,
+                                                 int B, int C, int HW, int ld, float guidance, float rescale, float p,
+                                                 float q, float a, float w0, float w1, float k1, float k2, float sn,
+                                                 uint64_t seed, int64_t sample_offset, int draw, void* stream) {
+    FD_PLAN(fd_cfg_rescale_multistep_step_f32(x, eps_nhwc, m0_out, m1, scale_out, z0, noise, mask, B, C, HW, ld, guidance,
+                                              rescale, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    const int rc = fd_rescale_args("fd_cfg_rescale_multistep_step_f32", eps_nhwc, B, C, HW, ld, rescale);
+    if (rc != FD_OK) return rc;
+    FD_CHECK_ARG(x && m0_out, FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: x or m0_out is null");
+    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: m0_out aliases the latents or m1");
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: mask without z0 / noise (null)");
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: z0 / noise alias the latents");
+    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, 1, 0,
+                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
+    if (sn != 0.f) {
+        const int rn = fd_noise_addr("fd_cfg_rescale_multistep_step_f32", seed, sample_offset, C * HW, draw, 0,
+                                     (unsigned long long)B * C * HW, &s.nz_addr);
+        if (rn != FD_OK) return rn;
+    }
+    return fd_latent_step_rescale(FD_STEP_MULTISTEP, s, rescale, scale_out, stream);
 }
 
 // One thread owns one Philox block: elements 4q..4q+3 of one sample, as far as the sample and the buffer reach.

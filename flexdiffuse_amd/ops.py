@@ -994,6 +994,52 @@ def cfg_multistep_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: to
              int(draw), hip.stream())
 
 
+def _check_scale_out(scale_out: Optional[torch.Tensor], B: int, like: torch.Tensor):
+    assert scale_out is None or (scale_out.dtype == torch.float32 and scale_out.is_contiguous() and scale_out.numel() == B
+                                 and scale_out.device == like.device), (None if scale_out is None else tuple(scale_out.shape), B)
+
+
+def cfg_rescale_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, HW: int, guidance: float,
+                          rescale: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False, do_step: bool = True,
+                          eps_out: Optional[torch.Tensor] = None, scale_out: Optional[torch.Tensor] = None, mask=None,
+                          sigma: float = 0.0, noise=None, draw: int = 0):
+    '''CFG + guidance rescale + DDIM step (fd_cfg_rescale_ddim_step_f32), in place on x (NCHW fp32): `cfg_ddim_step` with CFG
+    on and the guided output of each sample multiplied by f_b = rescale * std(cond) / std(guided) + 1 - rescale (-> scale_out,
+    fp32 [B], when given) before eps_out and the update; with mask = (z0, noise, mask [HW], k1, k2) the known-region blend of
+    `cfg_ddim_masked_step`; with sigma != 0 the step noise of `cfg_ddim_noise_step` from `noise` (a `PhiloxNoise`) at `draw`,
+    C * HW elements per sample.  do_step False: the combine alone into eps_out.  rescale == 0: the bits of the siblings.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * HW, x, eps_out, z0, nz)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, 2 * B * HW, C)
+    _check_scale_out(scale_out, B, eps_nhwc)
+    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+    assert not sigma or noise is not None, 'sigma without a PhiloxNoise'
+    hip.call('fd_cfg_rescale_ddim_step_f32', _p(x), eps_nhwc.data_ptr(), _p(eps_out), _p(scale_out), _p(z0), _p(nz), _p(mk),
+             B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), float(coef[0]), float(coef[1]), float(coef[2]),
+             float(coef[3]), int(v_prediction), int(do_step), float(k1), float(k2), float(sigma), seed, offset, int(draw),
+             hip.stream())
+
+
+def cfg_rescale_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor],
+                               B: int, C: int, HW: int, guidance: float, rescale: float, coef, mask=None,
+                               scale_out: Optional[torch.Tensor] = None, sn: float = 0.0, noise=None, draw: int = 0):
+    '''CFG + guidance rescale + DPM-Solver++ step (fd_cfg_rescale_multistep_step_f32): `cfg_multistep_step` (sn != 0:
+    `cfg_multistep_noise_step`, C * HW elements per sample) with CFG on and the guided output rescaled as in
+    `cfg_rescale_ddim_step`.  rescale == 0: the bits of those two.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, 2 * B * HW, C)
+    _check_scale_out(scale_out, B, eps_nhwc)
+    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+    assert not sn or noise is not None, 'sn without a PhiloxNoise'
+    hip.call('fd_cfg_rescale_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(scale_out),
+             _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), float(coef[0]),
+             float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn), seed, offset,
+             int(draw), hip.stream())
+
+
 def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
                    HW: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                    do_step: bool = True, eps_out: Optional[torch.Tensor] = None):

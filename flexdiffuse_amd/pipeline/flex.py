@@ -35,6 +35,11 @@ loop with fd_cfg_multistep_noise_step_f32; every other route hands the stream's 
 result depends on (seed, global sample index, step) only: not on the loop mode, the batch split or the rank count.  Without
 `step_noise`, `eta > 0` is the generator route as before.
 
+Guidance rescale (`guide.guidance_rescale`, beyond the reference; Lin et al. 2023 sec. 3.4): the guided output of each sample is
+scaled by a factor from two of its standard deviations, inside the step's own launch (fd_cfg_rescale_ddim_step_f32,
+fd_cfg_rescale_multistep_step_f32) on the fused loops and by the combine-only form of the first on the planned and generic
+routes -- the same bits on every route.  With 0 every route makes the calls it made before.
+
 fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 (and their two noise forms) are one kernel (csrc/step.hip) over one
 statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
 wherever they compute the same thing.
@@ -58,7 +63,7 @@ from .. import hip, ops
 from ..encode.clip import preprocess
 from ..noise import PhiloxNoise
 from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler
-from .guide import GuideBase, SimpleGuide
+from .guide import GuideBase, SimpleGuide, check_guidance_rescale
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
 VAE_SCALE = 0.18215
@@ -333,6 +338,10 @@ class FlexPipeline():
                 f'The value of strength should in [0.0, 1.0] but is {strength}')
         if mask_image is not None and init_image is None:
             raise ValueError('mask_image needs an init_image: the mask says which part of it to keep')
+        # guidance rescale: the guide's attribute, checked before any launch; 0 keeps every route on its calls
+        rescale = float(getattr(guide, 'guidance_rescale', 0.0) or 0.0)
+        if rescale:
+            check_guidance_rescale(rescale, guide.guidance)
         batch_size = guide.batch_size
         self.scheduler.set_timesteps(guide.steps)
         assert self.scheduler.timesteps is not None
@@ -394,6 +403,7 @@ class FlexPipeline():
                 and hasattr(self.unet, 'forward_nhwc'))
         simple = type(guide).noise_pred is SimpleGuide.noise_pred
         device_guide = simple or comp
+        rescale = rescale if simple else 0.0     # any other guide applies (or ignores) its own attribute in its noise_pred
         # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
         step_noise = self.step_noise
         sde = isinstance(self.scheduler, DPMSolverMultistepSDEScheduler)
@@ -461,7 +471,13 @@ class FlexPipeline():
                     sigma, coef = coef[4], coef[:4]
                     if debug:
                         latents = latents.clone()
-                    if noisy:
+                    if rescale:
+                        # CFG + rescale + DDIM update (+ sigma z, + the known-region blend) in one launch
+                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                        ops.cfg_rescale_ddim_step(latents, eps, B, C, H * W, guide.guidance, rescale, coef, vpred, mask=blend,
+                                                  sigma=float(sigma) if noisy else 0.0, noise=step_noise if noisy else None,
+                                                  draw=t_start + i)
+                    elif noisy:
                         # CFG + DDIM update + sigma z (+ the known-region blend of a masked request) in one launch
                         blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
                         ops.cfg_ddim_noise_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred, float(sigma),
@@ -484,7 +500,10 @@ class FlexPipeline():
                         eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
                     # masked img2img: the blend rides in the step's launch
                     blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                    if sde:
+                    if rescale:
+                        self.scheduler.fused_rescale_step(latents, eps, int(t), B, C, H * W, guide.guidance, rescale, blend,
+                                                          (step_noise, t_start + i) if sde else None)
+                    elif sde:
                         self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend,
                                                   (step_noise, t_start + i))
                     else:
@@ -500,6 +519,9 @@ class FlexPipeline():
                         noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
                         if comp:
                             guide.step(None, eps, eps_out=noise_pred)
+                        elif rescale:
+                            ops.cfg_rescale_ddim_step(None, eps, B, C, H * W, guide.guidance, rescale, do_step=False,
+                                                      eps_out=noise_pred)
                         else:
                             ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
                     else:

@@ -29,9 +29,23 @@ class GuideBase():
         raise NotImplementedError('noise_pred must be implemented.')
 
 
+def check_guidance_rescale(guidance_rescale: float, guidance: float):
+    '''ValueError unless 0 <= guidance_rescale <= 1, and classifier-free guidance is on whenever it is > 0.'''
+    if not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f'guidance_rescale should be in [0.0, 1.0] but is {guidance_rescale}')
+    if guidance_rescale > 0.0 and not guidance > 1.0:
+        raise ValueError(f'guidance_rescale {guidance_rescale} needs classifier-free guidance (guidance > 1, got {guidance}): '
+                         'it rescales the guided output')
+
+
 class SimpleGuide(GuideBase):
-    def __init__(self, encoder, unet, guidance: float, steps: int, clip_embeds: torch.Tensor):
+    def __init__(self, encoder, unet, guidance: float, steps: int, clip_embeds: torch.Tensor, *,
+                 guidance_rescale: float = 0.0):
+        '''`guidance_rescale` (beyond the reference; Lin et al. 2023 sec. 3.4, diffusers' `rescale_noise_cfg`): in [0, 1]; the
+        guided output of each sample is scaled towards the standard deviation of its conditional output.  A plain attribute,
+        read by FlexPipeline at every call; 0 is the reference's combine.'''
         GuideBase.__init__(self, encoder, unet, guidance, steps)
+        self.guidance_rescale = guidance_rescale
         self.embeds = clip_embeds
         self.batch_size = self.embeds.shape[0]
         self._stack = None
@@ -59,13 +73,18 @@ class SimpleGuide(GuideBase):
         eps = self.unet.forward_nhwc(latents, step, self.stacked_embeds(), rep=2 if cfg else 1)
         out = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
         # u + g (t - u)  (pipeline/guide.py:59-63), NHWC fp32 -> NCHW fp32
-        ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, self.guidance, do_step=False, eps_out=out)
+        if self.guidance_rescale:
+            check_guidance_rescale(self.guidance_rescale, self.guidance)
+            ops.cfg_rescale_ddim_step(None, eps, B, C, H * W, self.guidance, self.guidance_rescale, do_step=False, eps_out=out)
+        else:
+            ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, self.guidance, do_step=False, eps_out=out)
         return out
 
 
 class PromptGuide(SimpleGuide):
-    def __init__(self, encoder, unet, guidance: float, steps: int, prompt: Union[str, List[str]]):
-        SimpleGuide.__init__(self, encoder, unet, guidance, steps, encoder.prompt(prompt))
+    def __init__(self, encoder, unet, guidance: float, steps: int, prompt: Union[str, List[str]], *,
+                 guidance_rescale: float = 0.0):
+        SimpleGuide.__init__(self, encoder, unet, guidance, steps, encoder.prompt(prompt), guidance_rescale=guidance_rescale)
         self.prompt = prompt
 
 
@@ -78,10 +97,11 @@ class ScheduledGuide(SimpleGuide):
     the blended context is reprojected every step.'''
 
     def __init__(self, encoder, unet, guidance: float, steps: int, keyframes: Sequence[torch.Tensor],
-                 schedule: Sequence[float] = (0.0, 1.0), positions: Optional[Sequence[float]] = None, mode: str = 'lerp'):
+                 schedule: Sequence[float] = (0.0, 1.0), positions: Optional[Sequence[float]] = None, mode: str = 'lerp',
+                 *, guidance_rescale: float = 0.0):
         check_keyframes(keyframes)
         weights = step_weights(steps, len(keyframes), schedule, positions)
-        SimpleGuide.__init__(self, encoder, unet, guidance, steps, keyframes[0])
+        SimpleGuide.__init__(self, encoder, unet, guidance, steps, keyframes[0], guidance_rescale=guidance_rescale)
         self.keyframes = list(keyframes)
         B = self.batch_size
         if self.classifier_free_guidance:       # [uncond]*B + keyframe, as SimpleGuide.stacked_embeds stacks its one context

@@ -111,6 +111,10 @@ class Runner():
         # the generator's seed, batch k of B samples at sample offset k * B -- k sequential batches see the noise of one
         # batch of k * B
         self.step_noise = False
+        # opt-in (beyond the reference): guidance rescale of the guides `gen` and `gen_scheduled` build (`SimpleGuide(guidance_rescale=)`,
+        # Lin et al. 2023 sec. 3.4; 0.7 is what zero-terminal-SNR v-prediction checkpoints are published with).  An attribute
+        # like `step_noise`: the signatures of `gen` and `compose` are the reference's
+        self.guidance_rescale = 0.0
         # the models and tokenizer tables are millions of long-lived objects: a full collection over them is a 50-100 ms
         # host stall between denoising loops (measured in bench.py's timed region)
         if freeze_gc:
@@ -180,12 +184,12 @@ class Runner():
         unet, scale, steps = self.pipe.unet, given['guidance_scale'], given['steps']
         embeds = self.guide.embeds(prompt=given['prompt'], guide=given['guide'], **params)
         if travel is None:
-            g = SimpleGuide(self.encoder, unet, scale, steps, embeds)
+            g = SimpleGuide(self.encoder, unet, scale, steps, embeds, guidance_rescale=self.guidance_rescale)
         else:
             end_prompt, end_guide, schedule = travel
             end = self.guide.embeds(prompt=given['prompt'] if end_prompt is None else end_prompt,
                                     guide=given['guide'] if end_guide is _SAME else end_guide, **params)
-            g = ScheduledGuide(self.encoder, unet, scale, steps, [embeds, end], schedule)
+            g = ScheduledGuide(self.encoder, unet, scale, steps, [embeds, end], schedule, guidance_rescale=self.guidance_rescale)
         mask_image = given['mask_image']
         return self._run(given['samples'], g, given['init_image'], given['init_size'], given['strength'], given['debug'],
                          **({'mask_image': mask_image} if mask_image is not None else {}))

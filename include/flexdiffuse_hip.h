@@ -520,6 +520,34 @@ int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_o
                                     const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
                                     float guidance, float p, float q, float a, float w0, float w1, float k1, float k2,
                                     float sn, uint64_t seed, int64_t sample_offset, int per, int draw, void* stream);
+/* Guidance rescale on the device loop (additive; FD_ABI_VERSION stays 12): replaces diffusers' `rescale_noise_cfg` (Lin et
+ * al. 2023, "Common Diffusion Noise Schedules and Sample Steps Are Flawed", sec. 3.4) applied to the CFG combine of the
+ * reference's pipeline/guide.py:59-63 -- several torch reductions per step -- by one launch that also is the step.  CFG is
+ * implied: eps_nhwc has 2 * B * HW rows (unconditional half first), row stride ld >= C; the ld - C padding columns are
+ * never read.  Per sample b, over its n = C * HW elements, t the conditional value and e = u + g (t - u) the separately
+ * rounded fp32 value of the entry points above:
+ *   M2(v) = sum v^2 - (sum v)^2 / n  (the four sums in fp64) ;  f_b = float(rescale sqrt(max(M2(t), 0) / M2(e)) + (1 - rescale))
+ * evaluated in fp64 and rounded once; f_b = 1 when rescale == 0 or M2(e) <= 0.  The n - 1 of the two unbiased standard
+ * deviations cancels, so f_b is diffusers' factor.  Then, per element:  e = f_b e (one fp32 product) -> eps_out ;  the
+ * update ;  + sigma z ;  the blend ;  -> x -- everything after the product the arithmetic of the entry points above, so
+ * rescale == 0 gives their bits.  One workgroup per sample computes the statistics and runs the step (k_latent_step_rescale,
+ * csrc/step.hip): no atomics, no workspace, the same bits on every run.  scale_out (optional): fp32 [B], receives f_b.
+ * rescale outside [0, 1] is FD_EINVAL.
+ * fd_cfg_rescale_ddim_step_f32: the plain, masked (mask != NULL: z0, noise, k1, k2 as fd_cfg_ddim_masked_step_f32) and
+ * stochastic (sigma != 0: z as fd_cfg_ddim_noise_step_f32 with per = C * HW) DDIM steps.  do_step == 0 is the combine-only
+ * form: f_b e -> eps_out (required), x may be NULL, mask must be NULL and sigma 0. */
+int fd_cfg_rescale_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* scale_out, const float* z0,
+                                 const float* noise, const float* mask, int B, int C, int HW, int ld, float guidance,
+                                 float rescale, float c1, float c2, float c3, float c4, int v_prediction, int do_step,
+                                 float k1, float k2, float sigma, uint64_t seed, int64_t sample_offset, int draw,
+                                 void* stream);
+/* fd_cfg_multistep_step_f32 / fd_cfg_multistep_noise_step_f32 (sn != 0, per = C * HW) on the rescaled e: DPM-Solver++ (2M)
+ * and its SDE form. */
+int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1, float* scale_out,
+                                      const float* z0, const float* noise, const float* mask, int B, int C, int HW, int ld,
+                                      float guidance, float rescale, float p, float q, float a, float w0, float w1,
+                                      float k1, float k2, float sn, uint64_t seed, int64_t sample_offset, int draw,
+                                      void* stream);
 /* Context schedules (additive; FD_ABI_VERSION stays 12): out[i] = half_rn(a[i] + w * (b[i] - a[i])) on contiguous fp16 buffers of n
  * elements -- the subtraction, the product and the sum three separately rounded fp32 operations (no FMA), one rounding to half.
  * w == 0 stores a's bits, w == 1 stores b's bits; a[i] == b[i] gives a[i] for every w (a zero of either sign: +0 unless w is 0 or 1).
