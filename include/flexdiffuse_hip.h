@@ -318,14 +318,17 @@ typedef struct fd_attention_desc {
 
 int fd_attention_f16(const fd_attention_desc* desc, void* stream);
 
-/* Fused front half of the UNet's cross-attention at the 64x64 level (8 heads x 40 channels): the
+/* Fused front half of the UNet's cross-attention at the 64x64 level (8 heads x 40 channels, 256-row
+ * tiles) and at the 32x32 level (8 heads x 80 channels, 128-row tiles, two 320-column n-tiles): the
  * LayerNorm-fold q projection and softmax(Q K^T) V over the step-invariant text context (65..80
  * keys) in ONE launch -- replaces the q-projection fd_gemm_f16 launch and the fd_attention_f16
  * launch of diffusers' BasicTransformerBlock.attn2 inside `unet(...)` (reference
- * pipeline/guide.py:56-58); the query matrix never goes to HBM.
+ * pipeline/guide.py:56-58); the query matrix never goes to HBM.  Other shapes are refused (FD_ESHAPE).
  * fd_xattn_pack_kv_f16 packs the context's K [samples][n_keys][ldk] / V^T [samples][heads*head_dim][ldvt]
- * (the outputs of the to_k / to_v projections, computed once per context) into per-sample "images"
- * in MFMA fragment order, fd_xattn_image_bytes(heads, head_dim) bytes each (0 = unsupported shape). */
+ * (the outputs of the to_k / to_v projections, computed once per context; 1..80 keys, ldk >= heads*head_dim,
+ * ldvt >= n_keys; K rows and V^T columns >= n_keys are never read) into per-sample "images"
+ * in MFMA fragment order, fd_xattn_image_bytes(heads, head_dim) bytes each: 61440 at 8 x 40, 102400 at
+ * 8 x 80, 0 = unsupported shape.  Every byte of an image is written; key slots >= n_keys are zero. */
 int64_t fd_xattn_image_bytes(int heads, int head_dim);
 int fd_xattn_pack_kv_f16(const void* K, const void* Vt, void* k_image, void* v_image, int samples, int n_keys,
                          int heads, int head_dim, int ldk, int ldvt, int64_t k_sample_stride,
@@ -339,8 +342,8 @@ typedef struct fd_xattn_desc {
     const void* k_image;    /* [n_rep * M / rows_per_sample] images: replica r of sample b at index r * (M / rows_per_sample) + b */
     const void* v_image;
     void* out;              /* fp16 [n_rep * M][ldo]: attention output (heads concatenated), replica-major */
-    int32_t M, ldx, ldw, ldo;
-    int32_t rows_per_sample; /* query rows per sample; a multiple of 256 */
+    int32_t M, ldx, ldw, ldo; /* M: a multiple of the row tile; ldx, ldw multiples of 8, ldo of 4, all >= heads * head_dim; x, wq 16-byte, out 8-byte aligned */
+    int32_t rows_per_sample; /* query rows per sample; a multiple of the row tile (256 at head_dim 40, 128 at head_dim 80) that divides M */
     int32_t n_rep;           /* context replicas sharing the same queries (CFG fan-out of a shared prefix); >= 1 */
     int32_t n_keys, heads, head_dim;
     /* (ABI 12) ln_stats_parts = k in {2, 4, 8}: ln_stats holds the k partial slabs [k][M][2] (sum, sum of squares per 160-column tile) that the
