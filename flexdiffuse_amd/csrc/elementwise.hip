@@ -7,6 +7,16 @@
 #include "latent_step.h"
 
 // ---- NCHW fp32 -> NHWC fp16 (optionally replicated `rep` times along batch: CFG) ---------
+// y = half_rn(x * scale): ONE fp32 product, ONE rounding to half.  The product is kept an fp32 value of its own (the empty asm): the
+// compiler otherwise folds product and conversion into v_fma_mixlo_f16 (x * scale + 0), whose +0 addend turns a product of -0 into +0.
+__device__ __forceinline__ half_t fd_scale_to_half(float x, float scale) {
+    float p = x * scale;
+#if defined(__HIP_DEVICE_COMPILE__)
+    asm volatile("" : "+v"(p));
+#endif
+    return (half_t)p;
+}
+
 __global__ void k_nchw_to_nhwc(const float* __restrict__ x, half_t* __restrict__ y, int B, int C,
                                int HW, int rep, int Cpad, float scale) {
     const size_t total = (size_t)B * HW * Cpad;
@@ -16,7 +26,7 @@ __global__ void k_nchw_to_nhwc(const float* __restrict__ x, half_t* __restrict__
         const size_t r = e / Cpad;
         const int p = r % HW;
         const int b = r / HW;
-        const half_t v = c < C ? (half_t)(x[((size_t)b * C + c) * HW + p] * scale) : (half_t)0.f;
+        const half_t v = c < C ? fd_scale_to_half(x[((size_t)b * C + c) * HW + p], scale) : (half_t)0.f;
         for (int k = 0; k < rep; ++k) y[((size_t)(k * B + b) * HW + p) * Cpad + c] = v;
     }
 }
@@ -178,7 +188,9 @@ extern "C" int fd_im2col_f16(const void* x, void* y, int B, int Hi, int Wi, int 
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
     FD_CHECK_ARG(x && y && B > 0 && Hi > 0 && Wi > 0 && Cin > 0 && Ho > 0 && Wo > 0, FD_EINVAL,
                  "fd_im2col_f16: args");
-    FD_CHECK_ARG(k_pad >= KH * KW * Cin && k_pad % 8 == 0, FD_ESHAPE, "fd_im2col_f16: k_pad");
+    FD_CHECK_ARG(KH > 0 && KW > 0 && stride > 0 && pad_t >= 0 && pad_l >= 0, FD_EINVAL,
+                 "fd_im2col_f16: KH=%d, KW=%d, stride=%d must be positive, pad=(%d, %d) non-negative", KH, KW, stride, pad_t, pad_l);
+    FD_CHECK_ARG(k_pad >= 8 && k_pad % 8 == 0 && (int64_t)KH * KW * Cin <= k_pad, FD_ESHAPE, "fd_im2col_f16: k_pad");
     const size_t total = (size_t)B * Ho * Wo * k_pad;
     const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_im2col, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const half_t*)x,
@@ -205,8 +217,11 @@ extern "C" int fd_concat_channels_f16(const void* a, const void* b, void* out, i
     FD_PLAN(fd_concat_channels_f16(a, b, out, M, Ca, Cb, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
     FD_CHECK_ARG(a && b && out && M > 0, FD_EINVAL, "fd_concat_channels_f16: args");
+    FD_CHECK_ARG(Ca >= 0 && Cb >= 0 && (int64_t)Ca + Cb > 0, FD_EINVAL, "fd_concat_channels_f16: Ca=%d, Cb=%d (>= 0, not both 0)", Ca, Cb);
     FD_CHECK_ARG(Ca % 8 == 0 && Cb % 8 == 0, FD_ESHAPE, "fd_concat_channels_f16: C %% 8");
-    const size_t total = (size_t)M * (Ca + Cb) / 8;
+    FD_CHECK_ARG(((uintptr_t)a | (uintptr_t)b | (uintptr_t)out) % 16 == 0, FD_ESHAPE,
+                 "fd_concat_channels_f16: the pointers must be 16-byte aligned");
+    const size_t total = (size_t)M * ((size_t)(Ca + Cb) / 8);
     const int blocks = fd_grid1d(total, 8192);
     hipLaunchKernelGGL(k_concat, dim3(blocks), dim3(256), 0, (hipStream_t)stream, (const uint4*)a,
                        (const uint4*)b, (uint4*)out, (size_t)M, Ca / 8, Cb / 8);
@@ -296,6 +311,7 @@ extern "C" int fd_axpby_f32(const float* x, const float* y, float* out, int64_t 
 }
 
 // ---- CLIP text embeddings: out[b][l] = tok[ids[b][l]] + pos[l] --------------------------------
+// (an id outside [0, vocab) is clamped to the nearest valid row: 0 or vocab - 1)
 __global__ void k_embed_tokens(const long long* __restrict__ ids, const half_t* __restrict__ tok,
                                const half_t* __restrict__ pos, half_t* __restrict__ out, int L,
                                int D, int vocab) {
@@ -313,7 +329,7 @@ extern "C" int fd_embed_tokens_f16(const int64_t* ids, const void* tok_emb, cons
                                    void* out, int B, int L, int D, int vocab, void* stream) {
     FD_PLAN(fd_embed_tokens_f16(ids, tok_emb, pos_emb, out, B, L, D, vocab, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(ids && tok_emb && pos_emb && out && B > 0 && L > 0 && D > 0, FD_EINVAL,
+    FD_CHECK_ARG(ids && tok_emb && pos_emb && out && B > 0 && L > 0 && D > 0 && vocab > 0, FD_EINVAL,
                  "fd_embed_tokens_f16: args");
     hipLaunchKernelGGL(k_embed_tokens, dim3(B * L), dim3(256), 0, (hipStream_t)stream,
                        (const long long*)ids, (const half_t*)tok_emb, (const half_t*)pos_emb,

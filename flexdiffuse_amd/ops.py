@@ -890,6 +890,13 @@ def repeat_rows(x: torch.Tensor, rep: int, out: Optional[torch.Tensor] = None) -
 
 
 def concat_channels(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    '''[M][Ca] | [M][Cb] -> [M][Ca + Cb] (fd_concat_channels_f16 reads dense rows: a column slice is made dense first).'''
+    for t in (a, b):
+        if t.dim() != 2 or t.dtype != torch.float16 or t.stride(1) != 1:
+            raise ValueError(f'concat_channels: 2-D fp16 tensors with unit column stride, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
+    if a.shape[0] != b.shape[0]:
+        raise ValueError(f'concat_channels: {a.shape[0]} rows against {b.shape[0]}')
+    a, b = contiguous_rows(a), contiguous_rows(b)
     M = a.shape[0]
     out = _empty((M, a.shape[1] + b.shape[1]), torch.float16, a)
     hip.call('fd_concat_channels_f16', a.data_ptr(), b.data_ptr(), out.data_ptr(), M, a.shape[1],
@@ -1056,6 +1063,8 @@ def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: O
 
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
           exp_half_x: bool = False) -> torch.Tensor:
+    assert x.dtype == torch.float32 and (y is None or (y.dtype == torch.float32 and y.numel() == x.numel())), \
+        (x.dtype, tuple(x.shape), None if y is None else (y.dtype, tuple(y.shape)))
     x = x.contiguous()
     out = torch.empty_like(x)
     hip.call('fd_axpby_f32', x.data_ptr(), _p(y.contiguous() if y is not None else None),

@@ -403,13 +403,15 @@ int fd_softmax_rows_f16(void* x, int rows, int N, int ld, float scale, void* str
 /* ------------------------------------------------------------------------------------
  * Layout / elementwise helpers
  * ---------------------------------------------------------------------------------- */
-/* NCHW fp32 [B][C][HW] * scale -> NHWC fp16 [rep*B][HW][c_pad] (channels >= C zeroed). */
+/* NCHW fp32 [B][C][HW] * scale -> NHWC fp16 [rep*B][HW][c_pad] (channels >= C are +0, the rep replicas identical).
+ * Per element half_rn(x * scale): ONE fp32 product and ONE rounding to half (round to nearest even; -0 stays -0). */
 int fd_nchw_f32_to_nhwc_f16(const float* x, void* y, int B, int C, int HW, int rep, int c_pad,
                             float scale, void* stream);
-/* NHWC fp32 [B][HW][ld] -> NCHW fp32 [B][C][HW]: y = x*a + b, optionally clamped to [0,1]. */
+/* NHWC fp32 [B][HW][ld] -> NCHW fp32 [B][C][HW]: y = x*a + b, optionally clamped to [0,1].  The affine MAY BE FUSED (one FMA or a
+ * product and a sum rounded separately): |y - (x a + b)| <= 2^-24 (|x a| + |x a + b|) either way; the clamp follows the affine, so
+ * 0 <= y <= 1 exactly.  Columns C .. ld-1 of x are never read. */
 int fd_nhwc_f32_to_nchw_f32(const float* x, float* y, int B, int C, int HW, int ld, float a,
                             float b, int clamp01, void* stream);
-/* im2col for convolutions with fewer than 64 input channels; out [B*Ho*Wo][k_pad]. */
 /* (ABI 12) 3x3 / stride 1 / pad 1 convolution of a NARROW input (Cin <= 4) read straight from the fp32 NCHW tensor -- the UNet's conv_in
  * (reference pipeline/guide.py:56-58, the first layer of `unet(...)`; diffusers UNet2DConditionModel.conv_in):
  *   y[(b H + i) W + j][co] = bias[co] + sum_{ky, kx, ci} half(x[b][ci][i + ky - 1][j + kx - 1] * scale) * w[co][ky][kx][ci]
@@ -418,8 +420,13 @@ int fd_nhwc_f32_to_nchw_f32(const float* x, float* y, int B, int C, int HW, int 
  * of the first skip tensor.  One launch instead of fd_nchw_f32_to_nhwc_f16 + fd_im2col_f16 + fd_gemm_f16 (+ fd_repeat_rows_f16). */
 int fd_conv3x3_narrow_f16(const float* x, const void* w, const float* bias, void* y, int ldy, void* y2, int ldy2, int rep2,
                           int B, int Cin, int H, int W, int Cout, float scale, void* stream);
+/* im2col for convolutions with fewer than 64 input channels: NHWC fp16 x [B][Hi][Wi][Cin] -> out [B*Ho*Wo][k_pad] with
+ * out[(b Ho + oy) Wo + ox][(kh KW + kw) Cin + ci] = x[b][oy stride + kh - pad_t][ox stride + kw - pad_l][ci], +0 for taps outside the
+ * image and in columns KH KW Cin .. k_pad-1.  KH, KW, stride > 0, pads >= 0 (FD_EINVAL); k_pad >= KH KW Cin, a multiple of 8. */
 int fd_im2col_f16(const void* x, void* y, int B, int Hi, int Wi, int Cin, int Ho, int Wo, int KH,
                   int KW, int stride, int pad_t, int pad_l, int k_pad, void* stream);
+/* out[m] = [a[m] | b[m]] for dense fp16 rows: a [M][Ca], b [M][Cb], out [M][Ca + Cb].  Ca, Cb >= 0 and multiples of 8, not both 0
+ * (a zero-width half is legal; its pointer must still be non-NULL); all three pointers 16-byte aligned (FD_ESHAPE). */
 int fd_concat_channels_f16(const void* a, const void* b, void* out, int64_t M, int Ca, int Cb,
                            void* stream);
 /* Classifier-free guidance (pipeline/guide.py:59-63) fused with the DDIM update the
@@ -435,11 +442,18 @@ int fd_concat_channels_f16(const void* a, const void* b, void* out, int64_t M, i
 int fd_cfg_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, int B, int C, int HW,
                          int ld, int cfg, float guidance, float c1, float c2, float c3, float c4,
                          int v_prediction, int do_step, void* stream);
-/* out = a*x + b*y; with exp_half_x: out = exp(0.5 x) * y * b (VAE posterior sampling). */
+/* out = a*x + b*y; with exp_half_x: out = exp(0.5 x) * y * b (VAE posterior sampling).  Plain form: the two products and the sum
+ * are three SEPARATELY ROUNDED fp32 operations (no FMA), so the result has the bits of the same three host operations; y == NULL
+ * stands for y = 0 (a x = -0 then gives +0 for b >= 0).  out may be x itself (same base, in place): every element is read before it
+ * is written, by the same thread; a partial overlap is not supported. */
 int fd_axpby_f32(const float* x, const float* y, float* out, int64_t n, float a, float b,
                  int exp_half_x, void* stream);
+/* CLIP text embeddings: out[b][l] = half_rn(float(tok_emb[ids[b][l]]) + float(pos_emb[l])), tok_emb [vocab][D], pos_emb [L][D].
+ * An id outside [0, vocab) is CLAMPED: a negative id reads row 0, an id >= vocab reads row vocab-1.  vocab > 0 (FD_EINVAL). */
 int fd_embed_tokens_f16(const int64_t* ids, const void* tok_emb, const void* pos_emb, void* out,
                         int B, int L, int D, int vocab, void* stream);
+/* ViT embeddings: out[b][0] = half_rn(cls + pos[0]), out[b][1 + p] = half_rn(patches[b (T-1) + p] + pos[1 + p]) (fp32 sums);
+ * patches [B (T-1)][D], cls [D], pos [T][D], out [B T][D]; T > 1. */
 int fd_vit_assemble_f16(const void* patches, const void* cls, const void* pos, void* out, int B,
                         int T, int D, void* stream);
 /* diffusers Timesteps(flip_sin_to_cos=True, freq_shift=0): t fp32 -> fp16 [B][dim]; sample b reads
@@ -455,7 +469,8 @@ int fd_repeat_rows_f16(const void* src, int lds, void* dst, int ldd, int64_t row
 /* CompositeGuide region blend (reference composition/guide.py:86-98), NCHW fp32 [C][H][W]:
  * dst[:, oy:oy+sh, ox:ox+sw] += blend * (src - dst) on the same box.  oy, ox >= 0: the host
  * resolves Python's slice semantics (negative starts count from the end of the axis) first;
- * the box is clipped to the canvas. */
+ * the box is clipped to the canvas (nothing left, or sh / sw <= 0: FD_OK and no launch).  Per element d + blend (s - d) as three
+ * separately rounded fp32 operations; src is read inside the clipped box only. */
 int fd_region_blend_f32(float* dst, const float* src, int C, int H, int W, int oy, int ox, int sh,
                         int sw, float blend, void* stream);
 /* CompositeGuide on the device loop, one launch per step: the region blend of composition/guide.py:86-98
@@ -558,6 +573,7 @@ int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0
  * cached projections of its keyframes (UNet2DConditionModel.blend_context).  16-byte accesses when a, b and out are all 16-byte
  * aligned, a scalar kernel otherwise; out may alias neither input (FD_EINVAL, as are NULL pointers and n <= 0). */
 int fd_lerp_f16(const void* a, const void* b, void* out, int64_t n, float w, void* stream);
+/* Contiguous casts: fp32 -> fp16 rounds to nearest even (overflow to inf from 65520 on), fp16 -> fp32 is exact. */
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
 
