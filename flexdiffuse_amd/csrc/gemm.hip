@@ -270,7 +270,7 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_f16_dma(GemmArgs g, unsig
     const bool b2_staged = g.bias2 && g.bias_lds && ((EPI == 13 && g.ln_stats != nullptr) || (min(m0 + BM, g.M) - 1) / g.rows_per_batch == b_first);
     if (b2_staged || (EPI != 0 && EPI != 7)) {
         const __amdgpu_buffer_rsrc_t rsB2 = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(b2_staged ? (const void*)(g.bias2 + (size_t)b_first * g.ldb2) : (const void*)g.W), 0,
+            (void*)(b2_staged ? (const void*)(g.bias2 + (size_t)b_first * g.ldb2 + (EPI == 14 ? (size_t)z * g.strideBias : (size_t)0)) : (const void*)g.W), 0,
             b2_staged ? (unsigned)((g.N + 3) & ~3) * 4u : 0u, 0x00020000);
         if (wave * 64 + lane < BN)   // lanes past the tile would spill into the next LDS buffer
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsB2, (lds_ptr)(bias_s + BN + wave * 64), 4,
@@ -430,9 +430,12 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_f16_dma(GemmArgs g, unsig
     // LayerNorm fold fed with the producer's partial sums: this tile's rows are finalised into LDS here, behind the first DMAs (their wait is
     // the one the loop makes anyway); every barrier of the K loop lies between this write and the epilogue's reads
     float* const stats_s = bias_s + 4 * BN;
-    const bool ln_lds = (EPI == 5 || EPI == 6 || EPI == 7 || EPI == 13) && __builtin_amdgcn_readfirstlane(g.ln_parts > 1 ? 1 : 0) != 0;
+    const bool ln_lds = (EPI == 5 || EPI == 6 || EPI == 7 || EPI == 13 || EPI == 14) && __builtin_amdgcn_readfirstlane(g.ln_parts > 1 ? 1 : 0) != 0;
     if constexpr (EPI == 5 || EPI == 6 || EPI == 7 || EPI == 13) {
         if (ln_lds) ln_tile_stats_to_lds<BM>(g, m0, tid, stats_s);
+    }
+    if constexpr (EPI == 14) {   // (a batched fold: the statistics of batch z start at row z * M)
+        if (ln_lds) ln_tile_stats_to_lds<BM>(g, m0, tid, stats_s, z * g.M);
     }
     const lds_cfloat stats_tile = ln_lds ? (lds_cfloat)stats_s : (lds_cfloat) nullptr;
     if (NS == 2) {
@@ -561,6 +564,10 @@ __global__ __launch_bounds__(64 * WM * WN) void k_gemm_f16_dma(GemmArgs g, unsig
                 g, acc, m0 + wm * WTM + fr, n0 + wn * WTN, wn * WTN, fq, z, (lds_cfloat)bias_s, (lds_cfloat)(bias_s + BN),
                 nullptr, wm * WTM + fr, wn, m0, stats_tile);
         }
+    } else if constexpr (EPI == 14) {   // LayerNorm fold + per-head softmax (fd_gemm_desc.softmax_group): one wave column = one head
+        static_assert(WTN == 80, "softmax epilogue: 80-column wave tiles");
+        gemm_epilogue_softmax<MI, NI>(g, acc, m0 + wm * WTM + fr, n0 + wn * WTN, wn * WTN, fq, z, (lds_cfloat)bias_s, (lds_cfloat)(bias_s + BN),
+                                      wm * WTM + fr, stats_tile, z * g.M);
     } else if constexpr (EPI == 11 || EPI == 12) {   // lean (+ residual) + GroupNorm partial sums of the tile's output (gn_part_out)
         if constexpr (NS == 3) __syncthreads();
         gemm_epilogue_fast<MI, NI, FD_ACT_NONE, EPI == 12, true, false, false, WN, WM>(
@@ -995,7 +1002,7 @@ static int launch_mode(GemmArgs& g, int batch, hipStream_t st) {
     g.tiles_m = fd_cdiv(g.M, BM);
     g.tiles_n = fd_cdiv(g.N, BN);
     // stages + 2 x (bias, bias2 / colsum) tiles + the tile's LayerNorm statistics when they come as partial sums (ln_tile_stats_to_lds)
-    const size_t lds = NS * (size_t)(BM + BN) * 128 + 4 * BN * sizeof(float) + ((EPI == 5 || EPI == 6 || EPI == 7 || EPI == 13) ? BM * 2 * sizeof(float) : 0);
+    const size_t lds = NS * (size_t)(BM + BN) * 128 + 4 * BN * sizeof(float) + ((EPI == 5 || EPI == 6 || EPI == 7 || EPI == 13 || EPI == 14) ? BM * 2 * sizeof(float) : 0);
     dim3 grid(g.tiles_m * g.tiles_n, g.split_k, batch);
     // tensor extents for the buffer descriptors of the LDS-DMA loop (must fit 32 bits)
     const unsigned long long a_bytes =
@@ -1007,7 +1014,7 @@ static int launch_mode(GemmArgs& g, int batch, hipStream_t st) {
         if (lds > 64 * 1024 && fd_first_on_device(&configured)) {
             FD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_f16_dma<BM, BN, CONV, WM, TRANS, NS, WN, EPI>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            if constexpr (BN != 320 && EPI != 13)   // the 256x320 tile has no persistent form (it would spill); nor has the transposed tail
+            if constexpr (BN != 320 && EPI != 13 && EPI != 14)   // the 256x320 tile has no persistent form (it would spill); nor have the transposed tail / the softmax form
                 FD_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_gemm_f16_dmap<BM, BN, CONV, WM, TRANS, WN, EPI>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         }
@@ -1024,7 +1031,7 @@ static int launch_mode(GemmArgs& g, int batch, hipStream_t st) {
             if (persistent && g.bias2) return launch_mode<BM, BN, TRANS, CONV, WM, NS, WN, 0>(g, batch, st);
         }
         if (persistent) {
-            if constexpr (BN != 320 && EPI != 13) {
+            if constexpr (BN != 320 && EPI != 13 && EPI != 14) {
                 dim3 pgrid(g.tiles_m * g.tiles_n > slots ? slots : g.tiles_m * g.tiles_n, g.split_k, batch);
                 hipLaunchKernelGGL((k_gemm_f16_dmap<BM, BN, CONV, WM, TRANS, WN, EPI>), pgrid, dim3(64 * WM * WN), lds,
                                    st, g, (unsigned)a_bytes, (unsigned)w_bytes);
@@ -1128,6 +1135,8 @@ static int launch_epi(GemmArgs& g, int batch, hipStream_t st) {
     return launch<BM, BN, false, WM, NS, WN, 0>(g, batch, st);
 }
 
+#include "gemm_xfold.h"   // the launch forms of the context-folded cross-attention (fd_gemm_desc.softmax_group)
+
 // 1 when fd_gemm_f16 can honour fd_gemm_desc.ln_stats_out for an [M][N] fp16 output with row stride ldc and
 // (ldr > 0) a residual of row stride ldr: the row-complete 256x320 tile on the LDS-DMA path with the lean
 // epilogue and LDS-staged biases (FD_GEMM_FAST_EPI / FD_GEMM_BIAS_LDS / FD_GEMM_NO_DMA are A/B switches that
@@ -1159,7 +1168,18 @@ static int fd_stats_plan(int M, int N, int* tile, int batch = 1) {
         *tile = 23;
         return N / 160;
     }
+    // (64 rows per launch slice -- the 8x8 map with per-sample weights: the 64x160 tile, same slab layout)
+    if (N != 320 && batch > 1 && M % 64 == 0 && M % 128 != 0) {
+        *tile = 26;
+        return N / 160;
+    }
     if (N == 320 || M % 128 != 0) return 0;
+    // (per-sample weights at the 16x16 level -- launch 2 of the context-folded cross-attention, 16 x 256 x 1280 x 640: the 3-stage tile, 17.9 against
+    //  19.6 us on the 16-wave tile and 23.4 us on 256-row tiles, tools/ab_xattn_fold.py)
+    if (batch > 1 && M <= 256 && N >= 1280) {
+        *tile = 20;
+        return N / 160;
+    }
     *tile = (M % 256 == 0 && (long long)M * batch > 4096) ? 13 : 12;   // (the slab count does not depend on the tile)
     return N / 160;
 }
@@ -1290,16 +1310,20 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
     if (g.bias) FD_CHECK_ARG((uintptr_t)g.bias % 16 == 0, FD_ESHAPE, "fd_gemm_f16: bias align");
     if (g.res) FD_CHECK_ARG(d->ldr % 4 == 0, FD_ESHAPE, "fd_gemm_f16: ldr must be a multiple of 4");
     if (d->residual_rows) {
-        FD_CHECK_ARG(d->residual_rows > 0 && g.res && !d->conv && batch == 1 && !d->trans_out && g.M % d->residual_rows == 0 &&
-                         d->residual_rows % 32 == 0, FD_ESHAPE,
-                     "fd_gemm_f16: residual_rows=%d needs a residual, a linear GEMM, batch 1 and M=%d a multiple of it (itself a multiple of 32)",
+        // (batch > 1: the batches' output rows follow each other, row index = batch * M + m, and wrap together: no per-batch residual stride)
+        FD_CHECK_ARG(d->residual_rows > 0 && g.res && !d->conv && !d->trans_out && d->residual_rows % 32 == 0 &&
+                         (batch == 1 ? g.M % d->residual_rows == 0
+                                     : (d->batch_stride_res == 0 && d->batch_stride_c == (int64_t)g.M * g.ldc && g.M % 64 == 0 &&
+                                        ((long long)g.M * batch) % d->residual_rows == 0)), FD_ESHAPE,
+                     "fd_gemm_f16: residual_rows=%d needs a residual, a linear GEMM and M=%d (x batch, then with batch_stride_res 0, batch_stride_c = M ldc, M %% 64 == 0) "
+                     "a multiple of it (itself a multiple of 32)",
                      d->residual_rows, g.M);
         g.res_rows = d->residual_rows;
     }
 
     if (d->ln_stats) {
         // LayerNorm fold: C = act(rstd_m (A W'^T)[m][n] - rstd_m mean_m colsum_n + bias_n), W' = W diag(gamma)
-        FD_CHECK_ARG(d->ln_colsum && !d->conv && !d->bias2 && !d->residual && !d->out_f32 && batch == 1 &&
+        FD_CHECK_ARG(d->ln_colsum && !d->conv && !d->bias2 && !d->residual && !d->out_f32 && (batch == 1 || d->softmax_group > 0) &&
                          (d->act == FD_ACT_NONE || d->act == FD_ACT_GEGLU) && (d->alpha == 0.f || d->alpha == 1.f),
                      FD_EINVAL, "fd_gemm_f16: ln_stats needs ln_colsum, a linear GEMM, no bias2 / residual / fp32 "
                                 "output, act NONE or GEGLU, alpha 1");
@@ -1314,7 +1338,7 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         g.ldb2 = 0;
         if (d->ln_stats_parts > 0) {
             // the statistics come as the producer's partial slabs: each tile finalises its rows into LDS (ln_tile_stats_to_lds)
-            FD_CHECK_ARG((d->ln_stats_parts == 2 || d->ln_stats_parts == 4 || d->ln_stats_parts == 8) && d->ln_stats_rows >= d->M && g_use_dma,
+            FD_CHECK_ARG((d->ln_stats_parts == 2 || d->ln_stats_parts == 4 || d->ln_stats_parts == 8) && (long long)d->ln_stats_rows >= (long long)d->M * batch && g_use_dma,
                          FD_ESHAPE, "fd_gemm_f16: ln_stats_parts must be 2, 4 or 8 with ln_stats_rows >= M, on the LDS-DMA path");
             g.ln_parts = d->ln_stats_parts;
             g.ln_rows = d->ln_stats_rows;
@@ -1350,6 +1374,7 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         fd_prof_end(FD_FAMILY_GEMM, st2);
         return rc2;
     }
+    if (d->softmax_group > 0) return xfold_probs_impl(d, g, batch, stream, choice);   // gemm_xfold.h
     if (d->gn_out) {
         // GroupNorm(+SiLU) of the output inside the split-K finish (k_splitk_finish_gn)
         FD_CHECK_ARG(d->gn_gamma && d->gn_beta && d->gn_groups > 0 && d->N % d->gn_groups == 0 && d->N % 8 == 0 && d->M % g.rows_per_batch == 0,
@@ -1667,7 +1692,7 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         FD_CHECK_ARG(fd_gemm_pp_ok(g, batch, best_tile), FD_ESHAPE,
                      "fd_gemm_f16: ping-pong tile %d cannot run M=%d N=%d K=%d (full tiles, K %% 64 == 0, conv: Wo %% 8 == 0, no fused upsample)",
                      best_tile, g.M, g.N, g.K);
-    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile >= 30))
+    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile == 26 || best_tile >= 30))
         best_tile = best_tile == 4 ? 4 : -7;     // (reported by fd_gemm_plan as -7: the 128x128 generic kernel with the fold compiled in)
     if (choice) {
         if (choice[0] == -1) choice[2] = gn_parts_bm(g, best_tile, best_split, batch);   // fd_gemm_gn_parts_chunks
@@ -1684,10 +1709,15 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         FD_CHECK_ARG(best_split == 2 || best_split == 4 || best_split == 8 || best_split == 16, FD_ESHAPE,
                      "fd_gemm_f16: gn_out is honoured by split-K launches only (this one: tile %d, split_k %d); ask fd_gemm_plan first", best_tile, best_split);
     fd_prof_begin(FD_FAMILY_GEMM, st, flops, flops_exec, fd_tag(11u, g.M * batch, g.N, g.K + g.K2, best_tile * 64 + best_split, (g.mode << 8) | (g.act << 4) | (g.res ? 2 : 0) | (g.ln_stats ? 1 : 0)));
-    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile >= 30)) {
+    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile == 26 || best_tile >= 30)) {
         // small problems: the generic epilogue with the fold compiled in (64x64 for few rows)
         rc = best_tile == 4 ? launch_mode<64, 64, false, false, 2, 2, 2, 7>(g, batch, st)
                             : launch_mode<128, 128, false, false, 2, 2, 2, 7>(g, batch, st);
+        fd_prof_end(FD_FAMILY_GEMM, st);
+        return rc;
+    }
+    if (best_tile == 26) {   // 64 rows per launch slice (gemm_xfold.h)
+        rc = xfold_launch_out64(g, batch, st);
         fd_prof_end(FD_FAMILY_GEMM, st);
         return rc;
     }

@@ -66,6 +66,7 @@ struct GemmArgs {
     int ln_parts, ln_rows;
     float ln_inv_n, ln_eps_in;
     int res_rows;   // > 0: the residual row of output row m is m % res_rows (fd_gemm_desc.residual_rows; a multiple of the tile's rows)
+    int sm_valid;   // > 0: per-head softmax over the first sm_valid columns of every 80-column group (fd_gemm_desc.softmax_group / softmax_valid)
 };
 
 // Exact-form GELU  x * Phi(x),  Phi(x) = 0.5 * (1 + erf(x / sqrt 2)),  with erf from Abramowitz &
@@ -173,10 +174,11 @@ __device__ __forceinline__ void ln_tile_stats_body(const GemmArgs& g, const floa
     *reinterpret_cast<floatx2*>(dst) = floatx2{rstd, -mean * rstd};
 }
 
+// row_off: rows of the statistics in front of this launch slice's row 0 (batch z of a batched LayerNorm-fold launch: z * M)
 template <int BM>
-__device__ __forceinline__ void ln_tile_stats_to_lds(const GemmArgs& g, int m0, int tid, float* stats_s) {
+__device__ __forceinline__ void ln_tile_stats_to_lds(const GemmArgs& g, int m0, int tid, float* stats_s, int row_off = 0) {
     if (tid < BM) {
-        const int m = min(m0 + tid, g.M - 1);
+        const int m = min(m0 + tid, g.M - 1) + row_off;
         const float* p = g.ln_stats + 2 * (size_t)m;
         float* dst = stats_s + 2 * tid;
         switch (g.ln_parts) {
@@ -297,7 +299,8 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmArgs& g, floatx4 (&
         half_t* Cb = reinterpret_cast<half_t*>(g.C) + (size_t)z * g.strideC + (size_t)row0 * g.ldc + col0;
         if (g.phase) Cb = reinterpret_cast<half_t*>(g.C) + col0;   // rows are mapped per 16-row block below
         // (res_rows: a multiple of the tile's rows, so one wrap of the wave's first row serves its whole row block)
-        const int rrow0 = (RES && g.res_rows) ? row0 % g.res_rows : row0;
+        // (batch > 1 with res_rows: the batches' rows follow each other -- row index z * M + m -- and strideRes is 0)
+        const int rrow0 = (RES && g.res_rows) ? (z * g.M + row0) % g.res_rows : row0;
         const half_t* Rb = RES ? g.res + (size_t)z * g.strideRes + (size_t)rrow0 * g.ldr + col0 + fq * 4 : nullptr;
         floatx2 st_next = {g.alpha, 0.f};   // LNF: one row block ahead (see the GEGLU branch)
         if constexpr (LNF) LNF_STAT(st_next, 0)
@@ -455,6 +458,78 @@ __device__ __forceinline__ void gemm_epilogue_fast(const GemmArgs& g, floatx4 (&
 }
 
 #undef LNF_STAT
+
+// Lean LayerNorm-fold epilogue with a PER-HEAD SOFTMAX (fd_gemm_desc.softmax_group == 80): the GEMM's columns are the base-2 logits of
+// `heads` groups of 80 keys (W = the context-folded keys of one sample, scale * log2 e folded in), a wave tile is 80 columns wide -- exactly
+// one head -- so a row's 80 logits live in the 5 fragments x 4 registers of the 4 lanes that share the row (lane ^ 16, lane ^ 32):
+// exact row maximum, one pass, no LDS and no exchange between waves.  Columns >= sm_valid of a group are pad keys: left out of the
+// maximum and the sum, stored as 0.  The probabilities are stored normalised, fp16.  stats_off: see ln_tile_stats_to_lds(row_off).
+template <int MI, int NI>
+__device__ __forceinline__ void gemm_epilogue_softmax(const GemmArgs& g, floatx4 (&acc)[MI][NI], int row0, int col0, int coll, int fq, int z,
+                                                      lds_cfloat bias_tile, lds_cfloat colsum_tile, int trow0, lds_cfloat stats_tile,
+                                                      int stats_off) {
+    static_assert(NI == 5, "one wave column = one head of 80 keys");
+    typedef const __attribute__((address_space(3))) floatx4* lds_cf4;
+    const int pcol = (fq & 1) * 16 + (fq >> 1) * 8;
+    floatx4 bb[NI], cs[NI];
+#pragma unroll
+    for (int j = 0; j < NI; ++j) {
+        bb[j] = *reinterpret_cast<lds_cf4>(bias_tile + coll + j * 16 + fq * 4);
+        cs[j] = *reinterpret_cast<lds_cf4>(colsum_tile + coll + j * 16 + fq * 4);
+    }
+    half_t* Cb = reinterpret_cast<half_t*>(g.C) + (size_t)z * g.strideC + (size_t)row0 * g.ldc + col0;
+    const float* srow = g.ln_stats + 2 * ((size_t)stats_off + row0);
+    const int nval = g.sm_valid - fq * 4;   // column j * 16 + r of this lane is a real key iff j * 16 + r < nval
+#pragma unroll
+    for (int i = 0; i < MI; ++i) {
+        floatx2 st;
+        if (stats_tile) st = *reinterpret_cast<lds_cf2>(stats_tile + 2 * (trow0 + i * 16));
+        else st = *reinterpret_cast<const floatx2*>(srow + 2 * i * 16);
+        float v[NI][4];
+        float mx = -INFINITY;
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float s = fmaf(acc[i][j][r], st[0], fmaf(st[1], cs[j][r], bb[j][r]));
+                v[j][r] = (j * 16 + r < nval) ? s : -INFINITY;
+                mx = fmaxf(mx, v[j][r]);
+            }
+        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));   // finite: key 0 is always real (sm_valid >= 1)
+        float sum = 0.f;
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                v[j][r] = __builtin_amdgcn_exp2f(v[j][r] - mx);   // pad keys: 2^-inf = 0
+                sum += v[j][r];
+            }
+        sum += __shfl_xor(sum, 16, 64);
+        sum += __shfl_xor(sum, 32, 64);
+        const float inv = 1.0f / sum;
+        half4 oh[NI];
+#pragma unroll
+        for (int j = 0; j < NI; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) oh[j][r] = (half_t)(v[j][r] * inv);
+        half_t* Crow = Cb + (size_t)i * 16 * g.ldc;
+#pragma unroll
+        for (int j = 0; j < NI; j += 2) {
+            if (j + 1 < NI) {
+                const u32x2 x = __builtin_bit_cast(u32x2, oh[j]);
+                const u32x2 y = __builtin_bit_cast(u32x2, oh[j + 1 < NI ? j + 1 : j]);
+                unsigned x0 = x[0], x1 = x[1], y0 = y[0], y1 = y[1];
+                swap16(x0, y0);
+                swap16(x1, y1);
+                epi_store16<false>(Crow + j * 16 + pcol, u32x4{x0, x1, y0, y1});
+            } else {
+                *reinterpret_cast<half4*>(Crow + j * 16 + fq * 4) = oh[j];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);   // one row block at a time (see gemm_epilogue_fast)
+    }
+}
 
 // Fused epilogue shared by the register-staged and the LDS-DMA main loops.
 template <int BM, int BN, bool TRANS, int WM = 2, int WN = 2, bool LN = false>
@@ -686,7 +761,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g,
                 rb2[j] = floatx4{0.f, 0.f, 0.f, 0.f};
                 if (nb0 >= g.N) continue;
                 if (g.res)
-                    rres[j] = *reinterpret_cast<const half4*>(g.res + (size_t)z * g.strideRes + (size_t)(g.res_rows ? m % g.res_rows : m) * g.ldr + nb0);
+                    rres[j] = *reinterpret_cast<const half4*>(g.res + (size_t)z * g.strideRes + (size_t)(g.res_rows ? (z * g.M + m) % g.res_rows : m) * g.ldr + nb0);
                 if (b2_global) rb2[j] = *reinterpret_cast<const floatx4*>(g.bias2 + (size_t)b * g.ldb2 + nb0);
             }
         }
@@ -725,7 +800,7 @@ __device__ __forceinline__ void gemm_epilogue(const GemmArgs& g,
             if (g.res) {
                 half4 rr;
                 if constexpr (BATCH) rr = rres[j];
-                else rr = *reinterpret_cast<const half4*>(g.res + (size_t)z * g.strideRes + (size_t)(g.res_rows ? m % g.res_rows : m) * g.ldr + nb0);
+                else rr = *reinterpret_cast<const half4*>(g.res + (size_t)z * g.strideRes + (size_t)(g.res_rows ? (z * g.M + m) % g.res_rows : m) * g.ldr + nb0);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] += (float)rr[r];
             }

@@ -38,7 +38,7 @@ class fd_gemm_desc(ctypes.Structure):
                 ('gn_groups', c_int32), ('gn_silu', c_int32), ('gn_eps', c_float), ('gn_skip_c', c_int32),
                 ('gn_part_out', c_void_p), ('gn_part_chunks', c_int32), ('trans_n0', c_int32), ('C2', c_void_p),
                 ('sk_sync', c_void_p), ('ln_stats_parts', c_int32), ('ln_stats_rows', c_int32), ('ln_fold_eps', c_float),
-                ('residual_rows', c_int32)]
+                ('residual_rows', c_int32), ('softmax_group', c_int32), ('softmax_valid', c_int32)]
 
 
 class fd_attention_desc(ctypes.Structure):
@@ -698,6 +698,172 @@ def xattn_q(x: torch.Tensor, w: LinW, ln_stats: torch.Tensor, images: Tuple[torc
     if ln_stats.dim() == 3:
         d.ln_stats_parts, d.ln_fold_eps = ln_stats.shape[0], 1e-5
     hip.call('fd_xattn_q_f16', ctypes.byref(d), hip.stream())
+    return out
+
+
+# ------------------------------------------------------------- context-folded cross-attention
+# Cross-attention over a context that is fixed for the whole denoising loop, as TWO GEMMs:
+#   out = sum_h softmax(LN(x) Wq_h K_h^T) V_h Wo_h + bo + x = sum_h softmax(LN(x) K'_h) V'_h + bo + x
+# K'_h = Wq_h K_h^T and V'_h = V_h Wo_h are folded once per context (xattn_fold); a step runs xattn_fold_probs (LayerNorm-fold GEMM with
+# a per-head softmax epilogue, fd_gemm_desc.softmax_group) and xattn_fold_out (residual GEMM), both against per-sample weights.  It pays
+# where the hidden width heads x 80 is below C (C = 1280: less than half the MFMA work of q projection + attention + out projection).
+# FD_UNET_XATTN_FOLD=0: the unfolded launches everywhere (A/B).
+XATTN_FOLD = os.environ.get('FD_UNET_XATTN_FOLD', '1') != '0'
+XF_GROUP = 80   # columns per head of the folded operands (keys n_keys..79 are zero pads)
+
+
+@dataclass
+class XFold:
+    '''The folded context of one cross-attention layer.'''
+    kf: torch.Tensor     # [Be][heads * 80][C] fp16: row h * 80 + l = Wq'^T K_{h,l} (the weights of launch 1, K = C contiguous)
+    vf: torch.Tensor     # [Be][C][heads * 80] fp16: column h * 80 + l = Wo_h V_{h,l} (the weights of launch 2, K = heads * 80 contiguous)
+    rows: torch.Tensor   # [Be][2][heads * 80] fp32: (column sums of kf, folded q bias . K) -- ln_colsum and bias of launch 1
+    L: int
+
+
+def xattn_fold_layer(C: int, heads: int, n_keys: int) -> bool:
+    '''Layers whose context is folded: the two-GEMM form does less work than the unfolded launches only where heads x 80 < C.'''
+    return XATTN_FOLD and heads * XF_GROUP < C and 1 <= n_keys <= XF_GROUP and C % heads == 0 and (C // heads) % 8 == 0 and C % 160 == 0
+
+
+def xattn_fold(k: torch.Tensor, v: torch.Tensor, wq_t: torch.Tensor, wo: torch.Tensor, Be: int, L: int, heads: int,
+               out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    '''k, v [Be*L][C] fp16 (the cached key projection and the value projection, row-major), wq_t [C][C] fp16 = the gain-folded pre-scaled
+    q weight TRANSPOSED (row = input channel), wo [C][C] the out-projection weight -> (kf [Be][heads*80][C], vf [Be][C][heads*80]):
+    per head one small batched GEMM each (batch = samples), fp32 accumulation, one rounding.  `out`: rewritten in place (its pad rows /
+    columns must be zero and stay untouched).'''
+    C = k.shape[1]
+    dh, N = C // heads, heads * XF_GROUP
+    assert k.shape == v.shape == (Be * L, C) and k.stride(1) == 1 and v.stride(1) == 1 and wq_t.shape == (C, C) and wo.shape[0] == C
+    if out is None:
+        out = (torch.zeros((Be, N, C), dtype=torch.float16, device=k.device), torch.zeros((Be, C, N), dtype=torch.float16, device=k.device))
+    kf, vf = out
+    assert kf.shape == (Be, N, C) and vf.shape == (Be, C, N) and kf.is_contiguous() and vf.is_contiguous()
+    for h in range(heads):
+        d = fd_gemm_desc()      # kf[b][h*80 + l][:] = sum_j k[b*L + l][h*dh + j] wq_t[:][h*dh + j]
+        d.A, d.W, d.C = k.data_ptr() + 2 * h * dh, wq_t.data_ptr() + 2 * h * dh, kf.data_ptr() + 2 * h * XF_GROUP * C
+        d.M, d.N, d.K = L, C, dh
+        d.lda, d.ldw, d.ldc = k.stride(0), wq_t.stride(0), C
+        d.alpha, d.batch = 1.0, Be
+        d.batch_stride_a, d.batch_stride_w, d.batch_stride_c = L * k.stride(0), 0, N * C
+        hip.call('fd_gemm_f16', ctypes.byref(d), hip.stream())
+        d = fd_gemm_desc()      # vf[b][:][h*80 + l] = sum_j wo[:][h*dh + j] v[b*L + l][h*dh + j]
+        d.A, d.W, d.C = wo.data_ptr() + 2 * h * dh, v.data_ptr() + 2 * h * dh, vf.data_ptr() + 2 * h * XF_GROUP
+        d.M, d.N, d.K = C, L, dh
+        d.lda, d.ldw, d.ldc = wo.stride(0), v.stride(0), N
+        d.alpha, d.batch = 1.0, Be
+        d.batch_stride_a, d.batch_stride_w, d.batch_stride_c = 0, L * v.stride(0), C * N
+        hip.call('fd_gemm_f16', ctypes.byref(d), hip.stream())
+    return kf, vf
+
+
+def xattn_fold_rows(kf: torch.Tensor, k: torch.Tensor, bias_q: torch.Tensor, L: int, heads: int,
+                    out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    '''The two fp32 rows per sample launch 1 takes beside kf (fd_xattn_fold_rows_f32): [Be][2][heads*80] = (column sums of the ROUNDED
+    kf, folded q bias . K), from the buffers as they are -- in schedule mode after every blend, so they match the blended kf exactly.'''
+    Be, N, C = kf.shape
+    if out is None:
+        out = torch.empty((Be, 2, N), dtype=torch.float32, device=kf.device)
+    assert out.shape == (Be, 2, N) and out.is_contiguous() and kf.is_contiguous() and k.stride(1) == 1 and bias_q.dtype == torch.float32
+    hip.call('fd_xattn_fold_rows_f32', kf.data_ptr(), k.data_ptr(), bias_q.data_ptr(), out.data_ptr(), Be, L, heads, C // heads, C,
+             k.stride(0), hip.stream())
+    return out
+
+
+def _xf_probs_desc(x_ptr: int, lda: int, f_ptrs, B: int, HW: int, C: int, N: int, n_keys: int, out_ptr: int) -> 'fd_gemm_desc':
+    kf_ptr, rows_ptr = f_ptrs
+    d = fd_gemm_desc()
+    d.A, d.W, d.C = x_ptr, kf_ptr, out_ptr
+    d.ln_colsum, d.bias = rows_ptr, rows_ptr + 4 * N
+    d.M, d.N, d.K = HW, N, C
+    d.lda, d.ldw, d.ldc = lda, C, N
+    d.alpha, d.batch = 1.0, B
+    d.batch_stride_a, d.batch_stride_w, d.batch_stride_c, d.batch_stride_bias = HW * lda, N * C, HW * N, 2 * N
+    d.softmax_group, d.softmax_valid = XF_GROUP, n_keys
+    return d
+
+
+def xattn_fold_plan(B: int, HW: int, C: int, heads: int, n_keys: int, parts: int = 0, tile: int = 0) -> int:
+    '''The tile fd_gemm_f16 would run launch 1 on (24: 64 x 160, 25: 128 x 160), 0 when the library refuses the shape (a tile would hold
+    rows of two samples, more than 80 keys, operands of 2 GiB, off the LDS-DMA path): the caller then keeps the unfolded launches.
+    Host logic only (fd_gemm_plan).'''
+    N = heads * XF_GROUP
+    d = _xf_probs_desc(4096, C, (4096, 4096), B, HW, C, N, n_keys, 4096)
+    d.ln_stats = 4096
+    if parts:
+        d.ln_stats_parts, d.ln_stats_rows, d.ln_fold_eps = parts, B * HW, 1e-5
+    d.tile = tile
+    t, sp = c_int32(0), c_int32(0)
+    rc = hip.lib().fd_gemm_plan(ctypes.byref(d), ctypes.byref(t), ctypes.byref(sp))
+    return t.value if rc == 0 else 0
+
+
+def xattn_fold_probs(x: torch.Tensor, f: XFold, ln_stats: torch.Tensor, B: int, HW: int, n_keys: int, tile: int = 0) -> torch.Tensor:
+    '''Launch 1: P [B*HW][heads*80] fp16 = per-head softmax of LN-fold(x) kf[b]^T over the n_keys real keys (pad columns 0).
+    x [B*HW][C] the un-normalised hidden states, ln_stats their finished pairs [B*HW][2] or partial slabs [k][B*HW][2].'''
+    M, C = x.shape
+    N = f.kf.shape[1]
+    assert M == B * HW and x.stride(1) == 1 and f.kf.shape == (B, N, C) and f.rows.shape == (B, 2, N)
+    assert ln_stats.dtype == torch.float32 and ln_stats.is_contiguous()
+    out = _empty((M, N), torch.float16, x)
+    d = _xf_probs_desc(x.data_ptr(), x.stride(0), (f.kf.data_ptr(), f.rows.data_ptr()), B, HW, C, N, n_keys, out.data_ptr())
+    if ln_stats.dim() == 3:
+        assert ln_stats.shape[1:] == (M, 2) and ln_stats.shape[0] in (2, 4, 8), tuple(ln_stats.shape)
+        d.ln_stats_parts, d.ln_stats_rows, d.ln_fold_eps = ln_stats.shape[0], M, 1e-5
+    else:
+        assert ln_stats.shape == (M, 2)
+    d.ln_stats = ln_stats.data_ptr()
+    d.tile = tile
+    hip.call('fd_gemm_f16', ctypes.byref(d), hip.stream())
+    return out
+
+
+def _xf_out_desc(p_ptr: int, vf_ptr: int, bias_ptr, res_ptr, ldr: int, res_rows: int, B: int, HW: int, C: int, N: int, out_ptr: int,
+                 stats_ptr=None) -> 'fd_gemm_desc':
+    d = fd_gemm_desc()
+    d.A, d.W, d.C, d.bias, d.residual = p_ptr, vf_ptr, out_ptr, bias_ptr, res_ptr
+    d.M, d.N, d.K = HW, C, N
+    d.lda, d.ldw, d.ldc, d.ldr = N, N, C, ldr
+    d.alpha, d.batch = 1.0, B
+    d.batch_stride_a, d.batch_stride_w, d.batch_stride_c = HW * N, C * N, HW * C
+    if res_ptr and res_rows and res_rows != B * HW:
+        d.residual_rows = res_rows      # (the batches wrap together: no per-batch residual stride)
+    elif res_ptr:
+        d.batch_stride_res = HW * ldr
+    if stats_ptr:
+        d.ln_stats_out, d.ln_eps = stats_ptr, 1e-5
+    return d
+
+
+def xattn_fold_out_slabs(B: int, HW: int, C: int, N: int) -> int:
+    '''Slabs of LayerNorm partial sums launch 2 can write for its output (ln_stats_out [slabs][B*HW][2]); 0: run ln_row_stats.'''
+    if C <= 320 or C % 160 or not can_emit_row_stats(4096, C, N):
+        return 0
+    d = _xf_out_desc(4096, 4096, None, 4096, C, 0, B, HW, C, N, 4096, stats_ptr=4096)
+    t, sp = c_int32(0), c_int32(0)
+    return C // 160 if hip.lib().fd_gemm_plan(ctypes.byref(d), ctypes.byref(t), ctypes.byref(sp)) == 0 else 0
+
+
+def xattn_fold_out(p: torch.Tensor, f: XFold, bias: Optional[torch.Tensor], residual: Optional[torch.Tensor], B: int, HW: int,
+                   ln_stats_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    '''Launch 2: [B*HW][C] fp16 = P vf[b]^T + bias + residual (residual of fewer rows: read modulo its row count), optionally with the
+    LayerNorm partial sums of the output rows (ln_stats_out [C/160][B*HW][2]).'''
+    M, N = p.shape
+    C = f.vf.shape[1]
+    assert M == B * HW and p.is_contiguous() and f.vf.shape == (B, C, N)
+    if out is None:
+        out = _empty((M, C), torch.float16, p)
+    assert out.shape == (M, C) and out.is_contiguous()
+    rr = 0
+    if residual is not None:
+        assert residual.stride(1) == 1 and M % residual.shape[0] == 0
+        rr = residual.shape[0]
+    if ln_stats_out is not None:
+        assert ln_stats_out.shape[-2:] == (M, 2) and ln_stats_out.dtype == torch.float32 and ln_stats_out.is_contiguous()
+    d = _xf_out_desc(p.data_ptr(), f.vf.data_ptr(), _p(bias), _p(residual), residual.stride(0) if residual is not None else 0, rr, B, HW, C, N,
+                     out.data_ptr(), _p(ln_stats_out))
+    _sched(d, p.device)
+    hip.call('fd_gemm_f16', ctypes.byref(d), hip.stream())
     return out
 
 

@@ -111,6 +111,10 @@ class _Attn:
             self.ffp = ops.prep_linear(torch.cat([wp @ w2, wp], 1), g('.proj_out.bias').float() + wp @ b2, dev)
         self.ctx_kv = None  # (K [Be*L][C], V^T [Be][C][ldv]) of the cached text context
         self.ctx_img = None  # the same context packed for the fused q-projection + cross-attention kernel
+        # context-folded cross-attention (ops.xattn_fold: K' = Wq K^T and V' = V Wo once per context, two GEMMs per step) where
+        # heads x 80 < C: the transposed q weight the fold multiplies the cached keys with
+        self.q2t = self.q2.w.t().contiguous() if self.ln_fold and self.q_pre and ops.xattn_fold_layer(self.C, heads, 1) else None
+        self.ctx_fold = None  # ops.XFold of the cached context (None: the unfolded launches)
 
 
 class UNetOutput(SimpleNamespace):
@@ -247,7 +251,7 @@ class UNet2DConditionModel():
             # context gets buffers of its own (and ctx_generation moves: graphs / plans of the schedule read the arena)
             self._ctx_sched = None
             for a in self._attn_layers:
-                a.ctx_kv, a.ctx_img = None, None
+                a.ctx_kv, a.ctx_img, a.ctx_fold = None, None, None
         Be, L, D = ctx.shape
         c16 = ops.cast_f16(ctx.reshape(Be * L, D)) if ctx.dtype != torch.float16 \
             else ctx.reshape(Be * L, D).contiguous()
@@ -262,13 +266,21 @@ class UNet2DConditionModel():
                 ops.gemm_vt(c16, a.v2, Be, L, ldv, out=old[1])
             else:
                 a.ctx_kv = (ops.gemm(c16, a.k2), ops.gemm_vt(c16, a.v2, Be, L, ldv), L)
-                a.ctx_img = None
+                a.ctx_img, a.ctx_fold = None, None
                 realloc = True
             # 8 heads x 40 (the 64x64 level): K / V^T also packed in MFMA fragment order for fd_xattn_q_f16
             if a.ln_fold and a.q_pre and ops.xattn_supported(a.heads, a.C // a.heads, L, ops.xattn_row_tile(a.C // a.heads)):
                 a.ctx_img = ops.xattn_pack_kv(a.ctx_kv[0], a.ctx_kv[1], Be, L, a.heads, a.C // a.heads, out=a.ctx_img)
             else:
                 a.ctx_img = None
+            # C = 1280 (heads x 80 < C): the context folded through to_q and to_out, rewritten in place like K / V^T
+            if a.q2t is not None and ops.xattn_fold_layer(a.C, a.heads, L):
+                f = a.ctx_fold
+                kf, vf = ops.xattn_fold(a.ctx_kv[0], ops.gemm(c16, a.v2), a.q2t, a.o2.w, Be, L, a.heads, out=None if f is None else (f.kf, f.vf))
+                a.ctx_fold = ops.XFold(kf, vf, ops.xattn_fold_rows(kf, a.ctx_kv[0], a.q2.bias, L, a.heads, out=None if f is None else f.rows), L)
+                realloc = realloc or f is None
+            else:
+                a.ctx_fold = None
         if realloc:
             self.ctx_generation += 1
         self._ctx_key = key
@@ -276,8 +288,8 @@ class UNet2DConditionModel():
 
     # ---- context schedules (per-step blends of cached projections) ------------------------------
     def _ctx_layout(self, Be: int, L: int):
-        '''(halves per arena, per layer (K offset, V^T offset, image offsets or None, image bytes)) of one context's
-        projections laid out back to back, every buffer at a 16-byte aligned offset (8 halves).'''
+        '''(halves per arena, per layer (K offset, V^T offset, image offsets or None, image bytes, folded (K', V') offsets or None)) of one
+        context's projections laid out back to back, every buffer at a 16-byte aligned offset (8 halves).'''
         ldv = (L + 7) // 8 * 8
         up = lambda n: (n + 7) // 8 * 8      # noqa: E731
         off, slots = 0, []
@@ -290,17 +302,30 @@ class UNet2DConditionModel():
                 nb = hip.lib().fd_xattn_image_bytes(a.heads, d)
                 oi = (off, off + up(Be * nb // 2))
                 off = oi[1] + up(Be * nb // 2)
-            slots.append((ok, ov, oi, nb))
+            of = None
+            if a.q2t is not None and ops.xattn_fold_layer(a.C, a.heads, L):     # both linear in the context's K / V: they blend with them
+                n = Be * a.heads * ops.XF_GROUP * a.C
+                of = (off, off + up(n))
+                off = of[1] + up(n)
+            slots.append((ok, ov, oi, nb, of))
         return off, slots
 
     @staticmethod
     def _ctx_views(arena: torch.Tensor, slot, Be: int, L: int, C: int):
         '''((K, V^T, L), (K image, V^T image) or None) of one layer as views of `arena`.'''
-        ok, ov, oi, nb = slot
+        ok, ov, oi, nb = slot[:4]
         ldv = (L + 7) // 8 * 8
         kv = (arena[ok:ok + Be * L * C].view(Be * L, C), arena[ov:ov + Be * C * ldv].view(Be, C, ldv), L)
         img = None if oi is None else tuple(arena[o:o + Be * nb // 2].view(torch.uint8).view(Be, nb) for o in oi)
         return kv, img
+
+    @staticmethod
+    def _ctx_fold_views(arena: torch.Tensor, slot, Be: int, a: _Attn):
+        '''(folded keys [Be][heads*80][C], folded values [Be][C][heads*80]) of one layer as views of `arena`, or None.'''
+        if slot[4] is None:
+            return None
+        N, n = a.heads * ops.XF_GROUP, Be * a.heads * ops.XF_GROUP * a.C
+        return arena[slot[4][0]:slot[4][0] + n].view(Be, N, a.C), arena[slot[4][1]:slot[4][1] + n].view(Be, a.C, N)
 
     def set_context_keyframes(self, ctxs) -> torch.Tensor:
         '''Schedule mode: project every keyframe context (same shape (Be, L, D), at least two) exactly as set_context does --
@@ -323,6 +348,9 @@ class UNet2DConditionModel():
                    'handle': torch.zeros((Be, L, D), dtype=torch.float16, device=self.device)}
             for a, slot in zip(self._attn_layers, slots):
                 a.ctx_kv, a.ctx_img = self._ctx_views(arenas[-1], slot, Be, L, a.C)
+                fv = self._ctx_fold_views(arenas[-1], slot, Be, a)
+                # (the two fp32 rows of the fold are not linear data of the fp16 arena: blend_context recomputes them from the live buffers)
+                a.ctx_fold = None if fv is None else ops.XFold(fv[0], fv[1], torch.zeros((Be, 2, fv[0].shape[1]), dtype=torch.float32, device=self.device), L)
             self.ctx_generation += 1
         ldv = (L + 7) // 8 * 8
         for ctx, arena in zip(ctxs, sch['arenas']):
@@ -333,6 +361,9 @@ class UNet2DConditionModel():
                 ops.gemm_vt(c16, a.v2, Be, L, ldv, out=kv[1])
                 if img is not None:
                     ops.xattn_pack_kv(kv[0], kv[1], Be, L, a.heads, a.C // a.heads, out=img)
+                fv = self._ctx_fold_views(arena, slot, Be, a)
+                if fv is not None:
+                    ops.xattn_fold(kv[0], ops.gemm(c16, a.v2), a.q2t, a.o2.w, Be, L, a.heads, out=fv)
         sch['key'], sch['refs'], sch['live'] = key, list(ctxs), None
         self._ctx_sched = sch
         h = sch['handle']
@@ -351,8 +382,9 @@ class UNet2DConditionModel():
         return [self._ctx_views(sch['arenas'][i], slot, Be, L, a.C) for a, slot in zip(self._attn_layers, slots)]
 
     def blend_context(self, k: int, w: float):
-        '''live = key_k + w (key_{k+1} - key_k) over the whole arena: one fd_lerp_f16 on the current stream (K, V^T and the
-        packed images of every layer at once); nothing when the live arena already holds (k, w).'''
+        '''live = key_k + w (key_{k+1} - key_k) over the whole arena: one fd_lerp_f16 on the current stream (K, V^T, the packed images
+        and the folded K' / V' of every layer at once), then one fd_xattn_fold_rows_f32 per folded layer; nothing when the live arena
+        already holds (k, w).'''
         sch = self._ctx_sched
         if sch is None:
             raise RuntimeError('blend_context needs set_context_keyframes first (the UNet is not in schedule mode)')
@@ -362,6 +394,9 @@ class UNet2DConditionModel():
         if sch['live'] == (k, float(w)):
             return
         ops.lerp_f16(arenas[k], arenas[k + 1], float(w), out=arenas[-1])
+        for a in self._attn_layers:     # the folded layers' colsum / bias rows, from the blended buffers themselves
+            if a.ctx_fold is not None:
+                ops.xattn_fold_rows(a.ctx_fold.kf, a.ctx_kv[0], a.q2.bias, a.ctx_fold.L, a.heads, out=a.ctx_fold.rows)
         sch['live'] = (k, float(w))
 
     # ---- blocks -----------------------------------------------------------------------------
@@ -466,7 +501,19 @@ class UNet2DConditionModel():
         h = ops.gemm(o, a.o1, residual=h, ln_stats_out=st)
         kc, vtc, L = a.ctx_kv
         xt = x.t
-        if a.ctx_img is not None and HW % ops.xattn_row_tile(d) == 0:
+        fold = a.ctx_fold if ops.XATTN_FOLD and rep == 1 and a.ctx_fold is not None and a.ctx_fold.kf.shape[0] == B else None
+        if fold is not None:
+            # context-folded form: P = softmax_h(LN(h) K') and out = P V' + bo + h -- two launches instead of q projection, attention and
+            # out projection; a shape the library refuses (fd_gemm_plan) keeps the three launches
+            nparts = st.shape[0] if st is not None and st.dim() == 3 and ops.LN_PARTS and st.shape[0] in (2, 4, 8) else 0
+            if not ops.xattn_fold_plan(B, HW, C, a.heads, L, parts=nparts):
+                fold = None
+        if fold is not None:
+            p = ops.xattn_fold_probs(h, fold, fin(st, h, parts_ok=True), B, HW, L)
+            ns = ops.xattn_fold_out_slabs(B, HW, C, p.shape[1]) if emit else 0
+            st = torch.empty((ns, B * HW, 2), dtype=torch.float32, device=p.device) if ns > 1 else None
+            h = ops.xattn_fold_out(p, fold, a.o2.bias, h, B, HW, ln_stats_out=st)
+        elif a.ctx_img is not None and HW % ops.xattn_row_tile(d) == 0:
             # q projection + cross-attention in one launch (the query matrix never goes to HBM); `rep`
             # context replicas share the queries
             o = ops.xattn_q(h, a.q2, fin(st, h, parts_ok=True), a.ctx_img, HW, L, a.heads, d, n_rep=rep)
@@ -482,14 +529,17 @@ class UNet2DConditionModel():
                 for r in range(rep):
                     ops.attention(q2, kc[r * B * L:(r + 1) * B * L], vtc[r * B:(r + 1) * B], B, a.heads,
                                   HW, L, d, q_prescaled=a.q_pre, out=o[r * B * HW:(r + 1) * B * HW])
-        if rep > 1:
+        if fold is not None:
+            pass
+        elif rep > 1:
             # the fan-out of the shared prefix: h and the block input are only RESIDUALS from here on (of the out-projection and of the
             # block's last GEMM), which can read them modulo the prefix's rows (fd_gemm_desc.residual_rows) -- no replicas in HBM
             if not ops.residual_wrap_supported(B * HW, rep):
                 h, xt = ops.repeat_rows(h, rep), ops.repeat_rows(xt, rep)
             B = rep * B
-        st = mkst(B * HW)
-        h = ops.gemm(o, a.o2, residual=h, ln_stats_out=st)
+        if fold is None:
+            st = mkst(B * HW)
+            h = ops.gemm(o, a.o2, residual=h, ln_stats_out=st)
         if a.ln_fold:
             # (GEGLU at K <= 640 runs the persistent tile, which reads finished statistics only: the finalise launch stays there)
             f = ops.gemm(h, a.ff1, act=ops.ACT_GEGLU, ln_stats=fin(st, h, parts_ok=C >= 1280))

@@ -276,6 +276,17 @@ typedef struct fd_gemm_desc {
      * the same hidden states until the first cross-attention) without materialising the replicas.  Linear GEMM, batch 1,
      * M %% residual_rows == 0 and residual_rows a multiple of the tile's rows (256 covers every tile but the 288-row one).  0 = row m. */
     int32_t residual_rows;
+    /* (additive; FD_ABI_VERSION stays 12) PER-HEAD SOFTMAX of the output: the N columns are `N / softmax_group` groups of softmax_group = 80
+     * base-2 logits, of which the first softmax_valid (1..80) are real keys; C[m][group] = softmax over those, stored normalised fp16, the pad
+     * columns as 0.  This is launch 1 of the CONTEXT-FOLDED cross-attention of `unet(...)` (reference pipeline/guide.py:56-58; diffusers
+     * BasicTransformerBlock.attn2): the text context is fixed over the denoising loop, so to_q and K fold into K'_h = Wq_h K_h^T once per
+     * context and  P = softmax_h(LN(x) K')  is one LayerNorm-fold GEMM (ln_stats / ln_stats_parts) against per-sample weights -- batch = samples,
+     * batch_stride_w, and batch_stride_bias then advances `bias` AND `ln_colsum` (both [batch][N] fp32); the statistics of batch z are rows
+     * z * M .. of ln_stats (ln_stats_rows >= batch * M).  Launch 2 is an ordinary residual GEMM  P V' + bo + x  with V'_h = V_h Wo_h as its
+     * per-sample weights.  A wave tile is one head (80 columns): the softmax never leaves the wave.  Needs N %% 160 == 0, M %% 64 == 0 (rows per
+     * launch slice: a tile never holds rows of two samples), ldc %% 8 == 0, operands < 2 GiB, the LDS-DMA path; FD_ESHAPE otherwise -- ask
+     * fd_gemm_plan (tile 24: 64x160, 25: 128x160) and keep the unfolded launches for a refused shape.  0 = off. */
+    int32_t softmax_group, softmax_valid;
 } fd_gemm_desc;
 
 int fd_gemm_f16(const fd_gemm_desc* desc, void* stream);
@@ -295,6 +306,14 @@ int fd_gemm_can_fuse_groupnorm(int M, int N, int rows_per_sample, int groups, in
 /* (ABI 11) Row chunks per sample of fd_gemm_desc.gn_part_out for `d` (with d->gn_groups set): > 0 when fd_gemm_f16 will honour it with the
  * tile the rule picks, 0: run the statistics pass on the output instead.  Host logic only. */
 int fd_gemm_gn_parts_chunks(const fd_gemm_desc* d);
+/* (additive; FD_ABI_VERSION stays 12) The two fp32 rows per sample that launch 1 of the context-folded cross-attention (fd_gemm_desc.softmax_group)
+ * takes beside the folded keys kf [samples][heads * 80][C] fp16 (row h * 80 + l = Wq'^T K_{h,l}, pad rows zero):
+ *   rows[s][0][n] = sum_c kf[s][n][c]                              (ln_colsum: of the ROUNDED values, so a row mean cancels exactly)
+ *   rows[s][1][h * 80 + l] = sum_j bias_q[h * d + j] K[s * n_keys + l][h * d + j]   for l < n_keys, 0 for the pad keys   (bias)
+ * K [samples * n_keys][ldk] fp16 is the cached key projection, bias_q [heads * head_dim] fp32 the folded q bias.  Fixed summation order.
+ * C %% 8 == 0, head_dim %% 8 == 0, n_keys <= 80. */
+int fd_xattn_fold_rows_f32(const void* kf, const void* K, const float* bias_q, float* rows, int samples, int n_keys, int heads, int head_dim,
+                           int C, int ldk, void* stream);
 
 /* Flash attention forward (scores never leave registers).  Q [B][n_q][ldq], K [B][n_k][ldk]
  * with head h at column h*head_dim; Vt [B][heads*head_dim][ldvt] is V transposed (keys
