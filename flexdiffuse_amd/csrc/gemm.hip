@@ -989,13 +989,29 @@ extern "C" int fd_gemm_can_fuse_groupnorm(int M, int N, int rows_per_sample, int
 
 // --------------------------------------------------------------------------------------
 static bool g_use_dma = getenv("FD_GEMM_NO_DMA") == nullptr;
-static const int g_vae15 = 1;   // 256x256 tiles on the VAE widths (A/B closed in round 1: +19..33 %)
 static int g_tap_fast = getenv("FD_CONV_TAPFAST") ? atoi(getenv("FD_CONV_TAPFAST")) : 1;   // 1: 256x320 tile, 2: every conv tile
 static int g_pp = getenv("FD_GEMM_PP") ? atoi(getenv("FD_GEMM_PP")) : 1;   // 0: never pick the ping-pong tiles (A/B)
 static int g_bias_lds = getenv("FD_GEMM_BIAS_LDS") ? atoi(getenv("FD_GEMM_BIAS_LDS")) : 1;
 static int g_fast_epi = getenv("FD_GEMM_FAST_EPI") ? atoi(getenv("FD_GEMM_FAST_EPI")) : 1;   // 0: generic epilogue only (A/B)
 // 0 = never, 1 = short-K GEMMs only (default), 2 = always
 static int g_persist_mode = getenv("FD_GEMM_PERSIST") ? atoi(getenv("FD_GEMM_PERSIST")) : 1;
+
+// The LDS-DMA path with the lean epilogue and LDS-staged biases: what the statistics, softmax, transposed-tail and ping-pong forms need
+// (FD_GEMM_NO_DMA / FD_GEMM_FAST_EPI / FD_GEMM_BIAS_LDS are A/B switches that take it away)
+static bool gemm_lean_dma_path() { return g_use_dma && g_fast_epi && g_bias_lds; }
+
+// Extents of the operands in ELEMENTS (index of the last element read or written + 1; w without an appended K2).  The LDS-DMA loop's
+// buffer descriptors address a tensor through 32-bit BYTE offsets (< 2 GiB); the register-staged 4-wave kernel through 32-bit ELEMENT
+// offsets (< 2^31 halfs).  `conv`: A is the NHWC input of an implicit-GEMM convolution.
+struct GemmExtents {
+    unsigned long long a, w, c;
+    static bool below_2gib(unsigned long long elems) { return 2 * elems < 0x7fffffffull; }
+    bool dma_ok() const { return below_2gib(a) && below_2gib(w); }
+};
+static GemmExtents gemm_extents(const GemmArgs& g, bool conv) {
+    const unsigned long long a = conv ? ((unsigned long long)(g.M / (g.Ho * g.Wo)) * g.Hi * g.Wi - 1) * g.Cpix + g.Cin : (unsigned long long)(g.M - 1) * g.lda + g.K;
+    return {a, (unsigned long long)(g.N - 1) * g.ldw + g.K, (unsigned long long)(g.M - 1) * g.ldc + g.N};
+}
 
 template <int BM, int BN, bool TRANS, bool CONV, int WM = 2, int NS = 2, int WN = 2, int EPI = 0>
 static int launch_mode(GemmArgs& g, int batch, hipStream_t st) {
@@ -1137,12 +1153,7 @@ static int launch_epi(GemmArgs& g, int batch, hipStream_t st) {
 
 #include "gemm_xfold.h"   // the launch forms of the context-folded cross-attention (fd_gemm_desc.softmax_group)
 
-// 1 when fd_gemm_f16 can honour fd_gemm_desc.ln_stats_out for an [M][N] fp16 output with row stride ldc and
-// (ldr > 0) a residual of row stride ldr: the row-complete 256x320 tile on the LDS-DMA path with the lean
-// epilogue and LDS-staged biases (FD_GEMM_FAST_EPI / FD_GEMM_BIAS_LDS / FD_GEMM_NO_DMA are A/B switches that
-// take those away).  Callers that get 0 run fd_ln_row_stats_f16 on the output instead.
 // fraction of the CU slots busy over the launch's rounds (slots = 256 CUs x workgroups per CU)
-static const int g_t23 = 1;   // the 288x160 tile for row counts 9 * 2^k (A/B closed in round 3: c4 / c5 +16..18 %)
 static double fd_round_eff(long long tiles, int slots) {
     return (double)tiles / (double)((long long)slots * ((tiles + slots - 1) / slots));
 }
@@ -1152,7 +1163,7 @@ static double fd_round_eff(long long tiles, int slots) {
 static int fd_stats_plan(int M, int N, int* tile, int batch = 1) {
     if (N < 320 || N % 160 != 0) return 0;
     // rows = 9 x 2^k (768x768 images): the 288-row tile where it fills the rounds better than the 256-row shapes
-    const bool ok23 = g_t23 && M % 288 == 0 && M >= 1152;
+    const bool ok23 = M % 288 == 0 && M >= 1152;
     if (N == 320 && M % 256 == 0) {
         if (ok23 && fd_round_eff((long long)(M / 288) * 2, 256) > fd_round_eff(M / 256, 256) + 0.08) {
             *tile = 23;
@@ -1184,65 +1195,93 @@ static int fd_stats_plan(int M, int N, int* tile, int batch = 1) {
     return N / 160;
 }
 
+// 1 when fd_gemm_f16 can honour fd_gemm_desc.ln_stats_out for an [M][N] fp16 output with row stride ldc and
+// (ldr > 0) a residual of row stride ldr: the row-complete 256x320 tile on the LDS-DMA path with the lean
+// epilogue and LDS-staged biases (FD_GEMM_FAST_EPI / FD_GEMM_BIAS_LDS / FD_GEMM_NO_DMA are A/B switches that
+// take those away).  Callers that get 0 run fd_ln_row_stats_f16 on the output instead.
 extern "C" int fd_gemm_can_emit_row_stats(int M, int N, int K, int ldc, int ldr) {
-    if (!(g_use_dma && g_fast_epi && g_bias_lds)) return 0;
+    if (!gemm_lean_dma_path()) return 0;
     if (M <= 0 || K <= 0 || K % 8 != 0) return 0;
     if (ldc < N || (ldc & 7) != 0 || (ldr != 0 && (ldr < N || (ldr & 3) != 0))) return 0;
-    if (2ull * ((unsigned long long)(M - 1) * (unsigned long long)ldc + N) >= 0x7fffffffull) return 0;
+    if (!GemmExtents::below_2gib((unsigned long long)(M - 1) * (unsigned long long)ldc + N)) return 0;
     int tile = 0;
     return fd_stats_plan(M, N, &tile);   // slabs of partial sums the caller must provide and finalise (1: finalised in place)
 }
 
-static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice);
+// ---- fd_gemm_f16's host path: gemm_check validates the descriptor and fills the kernel argument, gemm_rule picks tile and split-K factor,
+// gemm_check_tile holds the checks that need that choice, gemm_launch launches.  fd_gemm_plan and fd_gemm_gn_parts_chunks stop before the launch.
+
+// What gemm_rule decides for a checked descriptor, and what the profile bracket of its launch records
+struct GemmPlan {
+    int tile, split, batch;
+    int gn_parts_bm;   // rows per chunk of the GroupNorm partial sums this launch can emit (fd_gemm_desc.gn_part_out); 0: it cannot
+    double flops, flops_exec;
+    unsigned tag;
+};
+
+// The launch forms.  All but the first are fixed kernels outside the tile rule; gemm_check marks them in the kernel argument.
+enum { FORM_RULE, FORM_TRANS_TAIL, FORM_SOFTMAX, FORM_TRANS_OUT };
+static int gemm_form(const GemmArgs& g) { return g.tr_n0 ? FORM_TRANS_TAIL : (g.sm_valid ? FORM_SOFTMAX : (g.trans_out ? FORM_TRANS_OUT : FORM_RULE)); }
+
+// (bm, bn) of the tiles with lean epilogues -- launch_epi's (the `switch (best_tile)` of gemm_launch_tile, tile 26) and the ping-pong ones;
+// 0 x 0 for every other id: the generic tiles of at most 256 x 160, unknown ids run the 128x128 default
+static void gemm_tile_shape(int tile, int* bm, int* bn) {
+    switch (tile) {
+        case 9: case 12: case 20: *bm = 128; *bn = 160; break;
+        case 10: *bm = 128; *bn = 128; break;
+        case 13: *bm = 256; *bn = 160; break;
+        case 14: *bm = 256; *bn = 128; break;
+        case 15: *bm = 256; *bn = 256; break;
+        case 16: *bm = 256; *bn = 320; break;
+        case 23: *bm = 288; *bn = 160; break;
+        case 26: *bm = 64; *bn = 160; break;
+        default: fd_gemm_pp_tile_shape(tile, bm, bn); break;   // gemm_pp.hip: 30 .. 33
+    }
+}
+
+// The tiles whose launcher (launch_epi, fd_gemm_pp_launch) dispatches the LayerNorm fold itself; on every other id the fold runs the small
+// generic kernels with it compiled in.  All of them but 26 (statistics epilogues only) also have the lean plain epilogue.
+static bool gemm_tile_ln_fold(int tile) {
+    return tile == 9 || tile == 10 || (tile >= 12 && tile <= 16) || tile == 20 || tile == 23 || tile == 26 || tile >= 30;
+}
+
+// fd_gemm_pp_ok (gemm_pp.hip) for a launch on `split` K slices: it reads the split from the kernel argument, hence the copy
+static bool gemm_pp_ok(GemmArgs g, int batch, int tile, int split) {
+    g.split_k = split;
+    return fd_gemm_pp_ok(g, batch, tile);
+}
+
+// Doubles the split-K factor while `tiles` x split stays short of `target` workgroups: at most `cap` slices of at least `min_kt` K-tiles each
+// whose fp32 slabs fit the workspace.  1 without a workspace or where N % 4 != 0 (the finish kernel sums four columns per thread).
+static int gemm_grow_split(const GemmArgs& g, size_t ws_bytes, long long tiles, int target, int cap, int min_kt) {
+    if (!g.ws || g.N % 4 != 0) return 1;
+    const int nk_all = (g.K + g.K2 + BK - 1) / BK;
+    int split = 1;
+    while (tiles * split < target && split < cap && nk_all / (split * 2) >= min_kt && (size_t)(split * 2) * g.M * g.N * 4 <= ws_bytes) split *= 2;
+    return split;
+}
 
 // Rows of the tile (= rows per chunk of the partial sums) when the launch of `g` on (tile, split) can emit GroupNorm partial sums
-// of its output (fd_gemm_desc.gn_part_out): a tile that spans the row (N == 320: the 256x320 tiles 16 / 30, the 128x320 tile 32) and lies
-// inside one sample, lean plain / residual epilogue; 0 otherwise.  The launchers check the same conditions.
-static int gn_parts_bm(const GemmArgs& g, int tile, int split, int batch) {
-    const int bm = (tile == 16 || tile == 30) ? 256 : (tile == 32 ? 128 : 0);
-    if (!bm || split != 1 || batch != 1 || g.N != 320 || !g_fast_epi || !g.bias_lds || !g_use_dma) return 0;
+// of its output (fd_gemm_desc.gn_part_out) in `groups` groups: a tile that spans the row (N == 320: the 256x320 tiles 16 / 30, the 128x320
+// tile 32) and lies inside one sample, lean plain / residual epilogue; 0 otherwise.  The launchers check the same conditions.
+static int gn_parts_bm(const GemmArgs& g, int tile, int split, int batch, int groups) {
+    int bm, bn;
+    gemm_tile_shape(tile, &bm, &bn);
+    if (bn != 320 || split != 1 || batch != 1 || g.N != 320 || !g_fast_epi || !g.bias_lds || !g_use_dma) return 0;
     if (g.out_f32 || g.trans_out || g.act != FD_ACT_NONE || g.ln_stats || g.ln_stats_out || g.phase || g.gn_out) return 0;
     if ((g.ldc & 7) || (g.res && (g.ldr & 3)) || g.M % bm || g.rows_per_batch % bm || g.M % g.rows_per_batch) return 0;
-    if (g.bias2 && g.rows_per_batch % bm) return 0;
-    if (g.gn_groups <= 0 || g.gn_groups > 128 || g.N % g.gn_groups || ((g.N / g.gn_groups) & 1)) return 0;
+    if (groups <= 0 || groups > 128 || g.N % groups || ((g.N / groups) & 1)) return 0;
     return bm;
 }
 
-extern "C" int fd_gemm_gn_parts_chunks(const fd_gemm_desc* d) {
-    int choice[3] = {-1, 0, 0};
-    if (!d || gemm_impl(d, nullptr, choice) != FD_OK || choice[2] <= 0) return 0;
-    const int rows = d->rows_per_sample > 0 ? d->rows_per_sample : d->M;
-    return rows / choice[2];
-}
-
-extern "C" int fd_gemm_f16(const fd_gemm_desc* d, void* stream) {
-    if (fd_plan_recording() && d) {
-        const fd_gemm_desc dc_ = *d;
-        fd_plan_push([dc_](void* fd_s_) -> int { return fd_gemm_f16(&dc_, fd_s_); });
-    }
-    return gemm_impl(d, stream, nullptr);
-}
-
-// The tile id and split-K factor fd_gemm_f16 would launch `d` with (after the same argument checks), without launching anything:
-// host logic only, no HIP call -- usable without a device (tests/test_gemm_rule_table.py pins the rule's choices on the launches
-// of the bench forward).  Pointers are only tested for NULL / alignment.
-extern "C" int fd_gemm_plan(const fd_gemm_desc* d, int* tile, int* split_k) {
-    FD_CHECK_ARG(tile && split_k, FD_EINVAL, "fd_gemm_plan: null output pointer");
-    int choice[2] = {0, 0};
-    const int rc = gemm_impl(d, nullptr, choice);
-    *tile = choice[0];
-    *split_k = choice[1];
-    return rc;
-}
-
-static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
+// Stage 1: the argument checks that do not depend on the tile, and the kernel argument.  No HIP call.
+static int gemm_check(const fd_gemm_desc* d, GemmArgs& g, int* batch_out) {
     FD_CHECK_ARG(d && d->A && d->W && (d->C || (d->gn_out && d->gn_skip_c)), FD_EINVAL, "fd_gemm_f16: null pointer");
     FD_CHECK_ARG(d->M > 0 && d->N > 0 && d->K > 0, FD_EINVAL, "fd_gemm_f16: M/N/K must be > 0");
     FD_CHECK_ARG(d->K % 8 == 0 && d->ldw % 8 == 0, FD_ESHAPE,
                  "fd_gemm_f16: K=%d and ldw=%d must be multiples of 8", d->K, d->ldw);
     FD_CHECK_ARG(((uintptr_t)d->A | (uintptr_t)d->W | (uintptr_t)d->C) % 16 == 0, FD_ESHAPE,
                  "fd_gemm_f16: pointers must be 16-byte aligned");
-    GemmArgs g;
     memset(&g, 0, sizeof(g));
     g.A = (const half_t*)d->A;
     g.W = (const half_t*)d->W;
@@ -1260,7 +1299,9 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
     g.act = d->act; g.out_f32 = d->out_f32; g.trans_out = d->trans_out;
     g.strideT = d->trans_sample_stride; g.ldt = d->trans_ld;
     g.alpha = d->alpha == 0.f ? 1.f : d->alpha;
-    const int batch = d->batch > 0 ? d->batch : 1;
+    g.split_k = 1;   // (gemm_launch writes the plan's)
+    g.bias_lds = g_bias_lds;
+    const int batch = *batch_out = d->batch > 0 ? d->batch : 1;
     if (d->conv) {
         g.mode = MODE_CONV;
         g.Hi = d->in_h; g.Wi = d->in_w; g.Cin = d->in_c; g.Ho = d->out_h; g.Wo = d->out_w;
@@ -1282,8 +1323,7 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
             // plain epilogue (it maps GEMM rows to the interleaved output pixels).
             FD_CHECK_ARG(batch == 4 && d->kh == 2 && d->kw == 2 && d->stride == 1 && d->out_h == d->in_h && d->out_w == d->in_w &&
                              d->batch_stride_a == 0 && d->batch_stride_c == 0 && !d->out_f32 && !d->residual && !d->bias2 &&
-                             d->act == FD_ACT_NONE && !d->trans_out && d->ldc % 8 == 0 &&
-                             g_fast_epi && g_bias_lds && g_use_dma,
+                             d->act == FD_ACT_NONE && !d->trans_out && d->ldc % 8 == 0 && gemm_lean_dma_path(),
                          FD_ESHAPE, "fd_gemm_f16: upsample2x == 2 needs batch 4, a 2x2 kernel, stride 1, out = in size, plain fp16 "
                                     "output and the lean epilogue on the LDS-DMA path");
         }
@@ -1297,16 +1337,15 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
                          (uintptr_t)d->A2 % 16 == 0 && d->ldw >= d->K + d->K2 && batch == 1 && !d->trans_out && !d->ln_stats,
                      FD_ESHAPE, "fd_gemm_f16: A2 / K2 need K %% 64 == 0, K2 %% 64 == 0, lda2 %% 8 == 0, ldw >= K + K2, "
                                 "16-byte aligned A2, no batch / transposed store / LayerNorm fold");
-        const unsigned long long a2b = 2ull * ((unsigned long long)(d->M - 1) * d->lda2 + d->K2);
-        FD_CHECK_ARG(a2b < 0x7fffffffull, FD_ESHAPE, "fd_gemm_f16: A2 >= 2 GiB");
-        g.A2 = (const half_t*)d->A2; g.lda2 = d->lda2; g.K2 = d->K2; g.a2_bytes = (unsigned)a2b;
+        const unsigned long long a2_elems = (unsigned long long)(d->M - 1) * d->lda2 + d->K2;
+        FD_CHECK_ARG(GemmExtents::below_2gib(a2_elems), FD_ESHAPE, "fd_gemm_f16: A2 >= 2 GiB");
+        g.A2 = (const half_t*)d->A2; g.lda2 = d->lda2; g.K2 = d->K2; g.a2_bytes = (unsigned)(2 * a2_elems);
     }
     if (g.act == FD_ACT_GEGLU)
         FD_CHECK_ARG(d->N % 32 == 0 && !d->trans_out && !d->out_f32 && !d->residual, FD_ESHAPE,
                      "fd_gemm_f16: GEGLU needs N %% 32 == 0, fp16 output, no residual");
     if (!d->trans_out && !(g.act == FD_ACT_GEGLU))
-        FD_CHECK_ARG(d->ldc % 4 == 0 && (d->N % 4 == 0 || true), FD_ESHAPE,
-                     "fd_gemm_f16: ldc must be a multiple of 4");
+        FD_CHECK_ARG(d->ldc % 4 == 0, FD_ESHAPE, "fd_gemm_f16: ldc must be a multiple of 4");
     if (g.bias) FD_CHECK_ARG((uintptr_t)g.bias % 16 == 0, FD_ESHAPE, "fd_gemm_f16: bias align");
     if (g.res) FD_CHECK_ARG(d->ldr % 4 == 0, FD_ESHAPE, "fd_gemm_f16: ldr must be a multiple of 4");
     if (d->residual_rows) {
@@ -1353,30 +1392,18 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
                      FD_EINVAL, "fd_gemm_f16: trans_n0 needs C2 and a plain LayerNorm-fold linear GEMM (act NONE, no residual / batch / appended operand)");
         FD_CHECK_ARG(d->M % 128 == 0 && d->N % 160 == 0 && d->trans_n0 % 160 == 0 && d->trans_n0 < d->N && g.rows_per_batch % 32 == 0 &&
                          d->M % g.rows_per_batch == 0 && d->trans_ld % 8 == 0 && d->trans_ld >= g.rows_per_batch && d->trans_sample_stride % 8 == 0 &&
-                         (uintptr_t)d->C2 % 16 == 0 && (d->ldc & 7) == 0 && g_use_dma && g_fast_epi && g_bias_lds,
+                         (uintptr_t)d->C2 % 16 == 0 && (d->ldc & 7) == 0 && gemm_lean_dma_path(),
                      FD_ESHAPE, "fd_gemm_f16: trans_n0 needs M %% 128 == 0, N and trans_n0 multiples of 160, rows_per_sample %% 32 == 0 and | M, "
                                 "trans_ld %% 8 == 0 and >= rows_per_sample, ldc %% 8 == 0, 16-byte aligned C2, the LDS-DMA path with the lean epilogue");
-        const unsigned long long ab = 2ull * ((unsigned long long)(d->M - 1) * d->lda + d->K), wb = 2ull * ((unsigned long long)(d->N - 1) * d->ldw + d->K);
-        FD_CHECK_ARG(ab < 0x7fffffffull && wb < 0x7fffffffull, FD_ESHAPE, "fd_gemm_f16: trans_n0: operands >= 2 GiB");
+        FD_CHECK_ARG(gemm_extents(g, false).dma_ok(), FD_ESHAPE, "fd_gemm_f16: trans_n0: operands >= 2 GiB");
         g.tr_n0 = d->trans_n0;
         g.C2 = (half_t*)d->C2;
-        g.split_k = 1;
-        g.bias_lds = g_bias_lds;
-        if (choice) {
-            choice[0] = 9;
-            choice[1] = 1;
-            return FD_OK;
-        }
-        hipStream_t st2 = (hipStream_t)stream;
-        const double fl = 2.0 * (double)d->M * d->N * d->K;
-        fd_prof_begin(FD_FAMILY_GEMM, st2, fl, fl, fd_tag(14u, g.M, g.N, g.K, g.tr_n0));
-        const int rc2 = launch_mode<128, 160, false, false, 4, 2, 2, 13>(g, 1, st2);
-        fd_prof_end(FD_FAMILY_GEMM, st2);
-        return rc2;
+        return FD_OK;
     }
-    if (d->softmax_group > 0) return xfold_probs_impl(d, g, batch, stream, choice);   // gemm_xfold.h
+    if (d->softmax_group > 0) return xfold_check(d, g, batch);   // gemm_xfold.h
     if (d->gn_out) {
-        // GroupNorm(+SiLU) of the output inside the split-K finish (k_splitk_finish_gn)
+        // GroupNorm(+SiLU) of the output inside the split-K finish (k_splitk_finish_gn), which adds residual row m without the wrap
+        FD_CHECK_ARG(!d->residual_rows, FD_EINVAL, "fd_gemm_f16: gn_out excludes residual_rows (the GroupNorm finish pass does not wrap the residual rows)");
         FD_CHECK_ARG(d->gn_gamma && d->gn_beta && d->gn_groups > 0 && d->N % d->gn_groups == 0 && d->N % 8 == 0 && d->M % g.rows_per_batch == 0,
                      FD_EINVAL, "fd_gemm_f16: gn_out needs gn_gamma, gn_beta, gn_groups | N, N %% 8 == 0 and whole samples (rows_per_sample | M)");
         FD_CHECK_ARG(!d->out_f32 && !d->trans_out && d->act == FD_ACT_NONE && batch == 1 && !d->ln_stats && !d->ln_stats_out &&
@@ -1395,39 +1422,44 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         FD_CHECK_ARG(!d->gn_out && (uintptr_t)d->sk_sync % 4 == 0, FD_EINVAL, "fd_gemm_f16: sk_sync excludes gn_out (the GroupNorm would read an unfinished tile)");
         g.sk_sync = (unsigned*)d->sk_sync;
     }
-    if (d->gn_part_out || (choice && choice[0] == -1)) {
-        g.gn_groups = d->gn_groups;
-        g.gn_part_out = d->gn_part_out;
-    }
-    hipStream_t st = (hipStream_t)stream;
-    // priced at the ALGORITHMIC work of the op it implements: the phase-decomposed upsample convolution (batch 4, K = 4 Cin)
-    // stands for a 3x3 convolution over the 4 M upsampled pixels (K = 9 Cin), of which it executes 4/9 of the MACs
-    const double flops_exec = 2.0 * (double)d->M * d->N * ((double)d->K + d->K2) * batch;
-    const double flops = (d->conv && d->upsample2x == 2 ? 2.25 : 1.0) * flops_exec;
-    g.split_k = 1;
-    g.bias_lds = g_bias_lds;
+    g.gn_part_out = d->gn_part_out;
+    if (g.gn_part_out) g.gn_groups = d->gn_groups;
     g.ws = (float*)d->workspace;
-    int rc;
-    if (d->trans_out) {
-        // 128x160 with 8 waves where 160 | N and the rows fill the chip: -16..18 % on the 64x64 / 32x32
-        // self-attention V projections (tools/ab_vt.py; 256x160 / 16 waves is no better, 16x16 maps tie).
-        // FD_GEMM_VT_TILE=0: the 128x64 / 4-wave tile everywhere (A/B)
-        static const int vt_tile = getenv("FD_GEMM_VT_TILE") ? atoi(getenv("FD_GEMM_VT_TILE")) : 9;
-        const bool vt160 = vt_tile && g.N % 160 == 0 && batch == 1 && g.M >= 8192 &&
-                           2ull * ((unsigned long long)(g.M - 1) * g.lda + g.K) < 0x7fffffffull;
-        if (choice) {
-            choice[0] = vt160 ? 9 : 3;      // (the transposed-store forms of the 128x160 / 128x64 tiles)
-            choice[1] = 1;
-            return FD_OK;
-        }
-        fd_prof_begin(FD_FAMILY_GEMM, st, flops, flops_exec, fd_tag(10u, g.M, g.N, g.K, vt160 ? 9 : 3));
-        if (vt160)
-            rc = g.ln_stats ? launch_mode<128, 160, true, false, 4, 2, 2, 7>(g, batch, st) : launch_mode<128, 160, true, false, 4, 2, 2, 0>(g, batch, st);
-        else
-        rc = g.ln_stats ? launch_mode<128, 64, true, false, 2, 2, 2, 7>(g, batch, st) : launch<128, 64, true>(g, batch, st);
-        fd_prof_end(FD_FAMILY_GEMM, st);
-        return rc;
+    if (d->trans_out) return FD_OK;
+    if (d->ln_stats_out) {
+        // N == 320: the 256x320 tile spans the whole row and finalises (rstd, -mean rstd) itself.  Wider rows (and N == 320
+        // at row counts the 288-row tile divides better): the 160-wide tiles write raw per-n-tile partial sums
+        // [N / 160][M][2] for fd_ln_finalize_stats_f32.  fd_gemm_can_emit_row_stats tells the caller which it will be.
+        int stile = 0;
+        // (batch > 1: the batches' rows must follow each other in C so that row index = batch * M + m)
+        FD_CHECK_ARG(fd_stats_plan(g.M, g.N, &stile, batch) > 0 && !d->conv && !d->trans_out && !d->out_f32 &&
+                         (batch == 1 || d->batch_stride_c == (int64_t)g.M * g.ldc), FD_ESHAPE,
+                     "fd_gemm_f16: ln_stats_out needs N == 320 with M %% 256 == 0, or N %% 160 == 0 with M %% 128 == 0 or M %% 288 == 0 (got M=%d N=%d)", g.M, g.N);
+        g.ln_stats_out = d->ln_stats_out;
+        g.stats_rows = g.M * batch;
+        g.ln_eps = d->ln_eps > 0.f ? d->ln_eps : 1e-5f;
     }
+    // The many-wave tiles exist only on the LDS-DMA path (operands < 2 GiB).  Larger operands go to the register-staged
+    // 4-wave kernel (< 2^31 halfs = 4 GiB); beyond that, refuse.
+    const GemmExtents ext = gemm_extents(g, g.mode == MODE_CONV);
+    FD_CHECK_ARG(ext.a < 0x7fffffffull && ext.w < 0x7fffffffull && ext.c < 0x7fffffffull, FD_ESHAPE,
+                 "fd_gemm_f16: operand of %llu elements exceeds the 2^31-element addressing limit; "
+                 "split the batch", ext.a > ext.w ? ext.a : ext.w);
+    // a per-batch bias is only staged by the LDS-DMA kernels (the global-memory fallbacks of the epilogues read bias[n])
+    FD_CHECK_ARG(g.strideBias == 0 || (batch > 1 && g.bias && g_use_dma && g.bias_lds && ext.dma_ok() && d->split_k <= 1),
+                 FD_ESHAPE, "fd_gemm_f16: batch_stride_bias needs batch > 1, a bias, the LDS-DMA path with LDS-staged biases and no split-K");
+    // the register-staged kernel knows neither the LayerNorm fold nor the producer statistics: refuse
+    // rather than hand the consumer GEMM uninitialised statistics
+    FD_CHECK_ARG(ext.dma_ok() || (!g.ln_stats && !g.ln_stats_out), FD_ESHAPE,
+                 "fd_gemm_f16: ln_stats / ln_stats_out need the LDS-DMA path (operands < 2 GiB); split the batch");
+    return FD_OK;
+}
+
+// Stage 2: the tile / split-K rule, as a function of the checked kernel argument, the descriptor's forced tile / split_k / workspace_bytes
+// and the process switches.  Launches nothing and leaves `g` alone.
+static void gemm_rule_tile(const GemmArgs& g, const fd_gemm_desc* d, GemmPlan* p) {
+    const int batch = p->batch;
+    const size_t ws_bytes = (size_t)d->workspace_bytes;
     // ---- tile / split-K selection (deterministic; rules fitted to an exhaustive sweep of
     // every (tile, split_k) over all GEMM shapes of the SD1.5 UNet + VAE on MI355X,
     // tools/sweep_gemm.py, profiles/r01_gemm_sweep.txt):
@@ -1438,6 +1470,7 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
     //  * when the tile count cannot fill 2 workgroups on each of the 256 CUs, split K until it
     //    does (fp32 slabs + fixed-order finish kernel, so results stay deterministic).
     const bool geglu = g.act == FD_ACT_GEGLU;
+    const bool pp = g_pp && gemm_lean_dma_path();   // FD_GEMM_PP=0: never pick the ping-pong tiles
     const int nk_all = (g.K + g.K2 + BK - 1) / BK;
     const bool n160 = (g.N % 160 == 0) && !geglu;
     const long long tiles_wide =
@@ -1451,17 +1484,14 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         if (g.N % 256 == 0 && (t15 % 256 == 0 || t15 >= 512 || (t15 >= 128 && t15 <= 256))) best_tile = 15;
         // K >= 1280 (the 16x16 and 8x8 levels, >= 20 K-tiles per tile): the ping-pong 256x256 tile, 3-8 % faster than the persistent
         // 16-wave tile; at K = 640 it is 3-5 % slower, at K = 320 (5 K-tiles: un-overlapped prologue + epilogue) 15 % slower
-        if (g_pp && g_use_dma && g_fast_epi && g_bias_lds && g.K >= 1280 && g.M % 256 == 0 && g.N % 256 == 0 && batch == 1 && !d->tile) {
-            g.split_k = 1;
-            if (fd_gemm_pp_ok(g, batch, 31)) best_tile = 31;
-        }
+        if (pp && g.K >= 1280 && g.M % 256 == 0 && g.N % 256 == 0 && batch == 1 && !d->tile && gemm_pp_ok(g, batch, 31, 1)) best_tile = 31;
     } else if (g.N <= 64) {
         best_tile = (g.M <= 64) ? 4 : 3;
         // the UNet's / VAE's output convolutions (N = 4 / 3, K = 9 C): 16 waves on 128x64; with <= 2 workgroups per CU two K slices
         // halve the serial K loop (conv_out of the bench forward: 41 vs 54 us, profiles/r05_gemm_sweep_vae.txt)
         if (g.mode == MODE_CONV && g.M >= 32768 && nk_all >= 32 && batch == 1) {
             best_tile = 11;
-            if (fd_cdiv(g.M, 128) <= 512 && g.N % 4 == 0 && g.ws && (size_t)2 * g.M * g.N * 4 <= (size_t)d->workspace_bytes) best_split = 2;
+            best_split = gemm_grow_split(g, ws_bytes, fd_cdiv(g.M, 128), 513, 2, 1);
         }
     } else if (g.K <= 640 || (g.K <= 1280 && tiles_wide < 512)) {
         // short K loops (transformer projections, GEGLU, 1x1 shortcuts) are latency-bound:
@@ -1477,33 +1507,24 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         // MAC than 256x160) wins 7-14 % when its tiles fill the 256 CUs in whole rounds
         if (g.N % 320 == 0 && ((long long)fd_cdiv(g.M, 256) * (g.N / 320) * batch) % 256 == 0) best_tile = 16;
         const long long tiles = (long long)fd_cdiv(g.M, 256) * fd_cdiv(g.N, 160) * batch;
-        if (batch == 1 && g.N % 4 == 0 && g.ws) {
-            while (tiles * best_split < 224 && best_split < 16 && nk_all / (best_split * 2) >= 4 &&
-                   (size_t)(best_split * 2) * g.M * g.N * 4 <= (size_t)d->workspace_bytes)
-                best_split *= 2;
-        }
+        if (batch == 1) best_split = gemm_grow_split(g, ws_bytes, tiles, 224, 16, 4);
     } else {
         // large K, other widths (VAE: 128/256/512): 256x128 with 16 waves when not split
         // (2-7 % over 128x128 with 8)
         best_tile = 1;
         long long tiles = tiles_wide;
         int target = 448;
-        if (g.M <= 2048 && !geglu) {
+        if (g.M <= 2048) {
             best_tile = 6;
             tiles = (long long)fd_cdiv(g.M, 256) * fd_cdiv(g.N, 128) * batch;
             target = 224;
         }
-        if (!geglu && batch == 1 && g.N % 4 == 0 && g.ws) {
-            while (tiles * best_split < target && best_split < 16 &&
-                   nk_all / (best_split * 2) >= 4 &&
-                   (size_t)(best_split * 2) * g.M * g.N * 4 <= (size_t)d->workspace_bytes)
-                best_split *= 2;
-        }
+        if (batch == 1) best_split = gemm_grow_split(g, ws_bytes, tiles, target, 16, 4);
         if (best_split == 1 && best_tile == 1) best_tile = (g.M >= 4096) ? 14 : 10;
         // VAE widths 256 / 512 on large maps: 256x256 with 64x64 wave tiles
-        // (36 % fewer LDS fragment reads per MAC than 256x128: +19..33 % on the 128^2..256^2 maps)
+        // (36 % fewer LDS fragment reads per MAC than 256x128: +19..33 % on the 128^2..256^2 maps; A/B closed in round 1)
         const long long t15 = (long long)fd_cdiv(g.M, 256) * (g.N / 256) * batch;
-        if (best_split == 1 && best_tile == 14 && g.N % 256 == 0 && g_vae15 && (t15 >= 1024 || t15 % 256 == 0))
+        if (best_split == 1 && best_tile == 14 && g.N % 256 == 0 && (t15 >= 1024 || t15 % 256 == 0))
             best_tile = 15;
     }
     // 16x16-resolution transformer GEMMs (M = 4096, N = 1280, K >= 1280): 256 tiles of 128x160, one per
@@ -1514,34 +1535,25 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
     // (only where its own 128x160 tiles fill most of the chip: swept at N >= 1280; a narrow N -- e.g. the batch-1
     // 4096x320x1280 FF-out -- would leave 64 workgroups on 256 CUs with split-K switched off)
     if (g.mode != MODE_CONV && n160 && g.M > 2048 && g.M <= 4096 && g.K >= 1280 && batch == 1 &&
-        (long long)fd_cdiv(g.M, 256) * (g.N / 160) < 256 && (long long)fd_cdiv(g.M, 128) * (g.N / 160) >= 200) {
+        (long long)fd_cdiv(g.M, 256) * (g.N / 160) < 256 && (long long)fd_cdiv(g.M, 128) * (g.N / 160) >= 200)
         best_tile = 20;
-        best_split = 1;
-    }
     // the parity-decomposed upsample convolution of a small map (16 x 8 x 8 -> 16 x 16: four slices of 1024 rows, no split-K in this mode):
     // 256-row tiles give 128 workgroups, the 3-stage 128x160 tile 256 -- 68 vs 90 us (tools/ab_up8.py; the fused-upsample form it replaces: 133 us)
     if (g.phase && n160 && g.M % 128 == 0 && g.K >= 1280 && (long long)fd_cdiv(g.M, 256) * (g.N / 160) * batch < 200 &&
-        (long long)(g.M / 128) * (g.N / 160) * batch >= 200) {
+        (long long)(g.M / 128) * (g.N / 160) * batch >= 200)
         best_tile = 20;
-        best_split = 1;
-    }
+    if (best_tile == 20) best_split = 1;   // (tile 20 comes from these two rules only)
     // Row counts of the form 9 x 2^k (768x768 images: 96x96 / 48x48 / 24x24 / 12x12 latents) leave the 256-row tiles
     // with 288-, 72- or 18-tile columns -- 2.25 rounds on 256 CUs, the last one a quarter full.  288 x 160 (12 waves,
-    // 48x80 wave tiles, otherwise the 256x160 kernel) divides those rows exactly: 73728 x 320 -> 512 tiles = 2 rounds.
-    if (g_t23 && n160 && g.M % 288 == 0 && g.M >= 1152 && (best_tile == 13 || best_tile == 12 || best_tile == 20)) {
-        const auto eff = [](long long t) { return (double)t / (double)(256 * ((t + 255) / 256)); };
+    // 48x80 wave tiles, otherwise the 256x160 kernel) divides those rows exactly: 73728 x 320 -> 512 tiles = 2 rounds
+    // (A/B closed in round 3: c4 / c5 +16..18 %).
+    if (n160 && g.M % 288 == 0 && g.M >= 1152 && (best_tile == 13 || best_tile == 12 || best_tile == 20)) {
         const int bm_cur = best_tile == 13 ? 256 : 128;
         const long long t_cur = (long long)fd_cdiv(g.M, bm_cur) * (g.N / 160) * batch * best_split;
-        long long t23 = (long long)(g.M / 288) * (g.N / 160) * batch;
-        int split23 = 1;
-        if (best_split > 1 || (g.K + g.K2 > 1280 && batch == 1 && g.N % 4 == 0 && g.ws)) {
-            while (t23 * split23 < 224 && split23 < 16 && nk_all / (split23 * 2) >= 4 &&
-                   (size_t)(split23 * 2) * g.M * g.N * 4 <= (size_t)d->workspace_bytes)
-                split23 *= 2;
-        }
+        const long long t23 = (long long)(g.M / 288) * (g.N / 160) * batch;
+        const int split23 = (best_split > 1 || (g.K + g.K2 > 1280 && batch == 1)) ? gemm_grow_split(g, ws_bytes, t23, 224, 16, 4) : 1;
         // (128-row tiles run two workgroups per CU: their rounds are 512 slots)
-        const double e_cur = bm_cur == 256 ? eff(t_cur) : (double)t_cur / (double)(512 * ((t_cur + 511) / 512));
-        if (eff(t23 * split23) > e_cur + 0.08) {
+        if (fd_round_eff(t23 * split23, 256) > fd_round_eff(t_cur, bm_cur == 256 ? 256 : 512) + 0.08) {
             best_tile = 23;
             best_split = split23;
         }
@@ -1551,176 +1563,177 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
     // over K until ~every CU has a workgroup -- or 128x320 tiles (+7..18 %), and the long-K linears of the feed-forward output
     // (+13..14 %).  Convolutions with the ResBlock shortcut appended (their A2 rows stream from HBM inside a few K-tiles),
     // GEGLU and the short-K projections stay on the 2-barrier kernels (equal or faster there); FD_GEMM_PP=0 switches the rule off.
-    if (g_pp && g_use_dma && g_fast_epi && g_bias_lds && !geglu && !d->ln_stats_out && (!g.ln_stats || g.mode != MODE_CONV) && (batch == 1 || g.phase) && !g.out_f32 &&
+    if (pp && !geglu && !d->ln_stats_out && (!g.ln_stats || g.mode != MODE_CONV) && (batch == 1 || g.phase) && !g.out_f32 &&
         g.act == FD_ACT_NONE && g.N % 320 == 0 && g.M % 128 == 0 && (g.ldc & 7) == 0 && (!g.res || (g.ldr & 3) == 0)) {
         // (the lean epilogue takes a per-sample bias only from tiles that lie in one sample; split-K launches leave it to the finish kernel)
         const bool b2ok = !g.bias2 || g.rows_per_batch % 256 == 0;
         // (the parity-decomposed upsample convolution is four launch slices -- blockIdx.z -- of the same tile grid: no split-K there)
         const long long t30 = (g.M % 256 == 0 ? (long long)(g.M / 256) * (g.N / 320) : 0) * batch, t32 = (long long)(g.M / 128) * (g.N / 320) * batch;
+        const auto fills = [](long long tiles) { return tiles >= 200 && fd_round_eff(tiles, 256) >= 0.85; };
         int tile = 0, split = 1;
         if (g.mode == MODE_CONV && g.phase) {
-            if (t30 >= 200 && fd_round_eff(t30, 256) >= 0.85 && nk_all >= 32) tile = 30;     // tools/.. rule guard: 168 vs 182 us at 32x32 -> 64x64
+            if (fills(t30) && nk_all >= 32) tile = 30;     // tools/.. rule guard: 168 vs 182 us at 32x32 -> 64x64
         } else if (g.mode == MODE_CONV && !g.K2 && nk_all >= 32) {
-            if (t30 >= 200 && fd_round_eff(t30, 256) >= 0.85) {
+            if (fills(t30)) {
                 tile = 30;
             } else if (t30 > 0) {
-                while (t30 * split < 200 && split < 4 && nk_all / (split * 2) >= 24 && g.ws && g.N % 4 == 0 &&
-                       (size_t)(split * 2) * g.M * g.N * 4 <= (size_t)d->workspace_bytes)
-                    split *= 2;
-                if (t30 * split >= 200 && fd_round_eff(t30 * split, 256) >= 0.85) tile = 30;
+                split = gemm_grow_split(g, ws_bytes, t30, 200, 4, 24);
+                if (fills(t30 * split)) tile = 30;
                 // two K slices of a short K loop lose to whole 128x320 tiles (the slab round trip + finish launch are fixed costs)
-                if (tile == 30 && split == 2 && nk_all < 150 && b2ok && t32 >= 200 && fd_round_eff(t32, 256) >= 0.85) {
+                if (tile == 30 && split == 2 && nk_all < 150 && b2ok && fills(t32)) {
                     tile = 32;
                     split = 1;
                 }
             }
-            if (!tile && b2ok && t32 >= 200 && fd_round_eff(t32, 256) >= 0.85) tile = 32, split = 1;
+            if (!tile && b2ok && fills(t32)) tile = 32, split = 1;
             // few rows, long K (the 8x8 level: 1024 x 1280 x 11520 / 23040): 128x320 tiles x up to 8 K slices -- 44.4 vs 46.0 / 66.8 vs 71.4 us
             // against 256x160 x 8 on the 2-barrier kernel (4 launches each, profiles/r05_gemm_sweep_vae.txt header run)
             if (!tile && t32 > 0) {
-                int s8 = 1;
-                while (t32 * s8 < 200 && s8 < 8 && nk_all / (s8 * 2) >= 8 && g.ws && g.N % 4 == 0 &&
-                       (size_t)(s8 * 2) * g.M * g.N * 4 <= (size_t)d->workspace_bytes)
-                    s8 *= 2;
-                if (s8 > 1 && t32 * s8 >= 200 && fd_round_eff(t32 * s8, 256) >= 0.85) tile = 32, split = s8;
+                const int s8 = gemm_grow_split(g, ws_bytes, t32, 200, 8, 8);
+                if (s8 > 1 && fills(t32 * s8)) tile = 32, split = s8;
             }
         } else if (g.mode != MODE_CONV && (g.K + g.K2 >= 1280 || (g.K + g.K2 >= 640 && g.N >= 1280))) {
             // FF-out (+ folded proj_out, + residual) and the wide LayerNorm-folded projections (fused q|k at the 32x32 / 16x16 levels:
             // 30.6 vs 35.0 us and 29.1 vs 32.0 us, tools/ab_pp_recorded.py)
-            if (t30 >= 200 && fd_round_eff(t30, 256) >= 0.85) tile = 30;
-            else if (t32 >= 200 && fd_round_eff(t32, 256) >= 0.85) tile = 32;
+            if (fills(t30)) tile = 30;
+            else if (fills(t32)) tile = 32;
         }
         if (split == 1 && !b2ok) tile = 0;
-        if (tile) {
-            g.split_k = split;
-            if (fd_gemm_pp_ok(g, batch, tile)) {
-                best_tile = tile;
-                best_split = split;
-            }
-            g.split_k = 1;
+        if (tile && gemm_pp_ok(g, batch, tile, split)) {
+            best_tile = tile;
+            best_split = split;
         }
     }
     // ... and the VAE decoder's widths (N = 256 / 512, no 160-wide tiles): the ping-pong 256x256 tile is 3-8 % faster than the 2-barrier 256x256
     // tile on its convolutions from the 64x64 maps up (profiles/r05_gemm_sweep_vae.txt), 10-18 % on its K = 512 attention projections, 160 vs 213 us on the
     // mid-block attention's batched QK^T (8 x 4096 x 4096 x 512)
-    if (g_pp && g_use_dma && g_fast_epi && g_bias_lds && !geglu && !n160 && !d->ln_stats_out && !g.ln_stats && !g.out_f32 && !d->trans_out && g.act == FD_ACT_NONE &&
+    if (pp && !geglu && !n160 && !d->ln_stats_out && !g.ln_stats && !g.out_f32 && !d->trans_out && g.act == FD_ACT_NONE &&
         best_split == 1 && g.N % 256 == 0 && g.M % 256 == 0 && (g.ldc & 7) == 0 && (!g.res || (g.ldr & 3) == 0) &&
         (!g.bias2 || g.rows_per_batch % 256 == 0)) {
         const long long t31 = (long long)(g.M / 256) * (g.N / 256) * batch;
         const bool pick = g.mode == MODE_CONV ? (nk_all >= (g.phase ? 16 : 32) && t31 >= (g.phase ? 512 : 256)) : (g.K >= 512 && t31 >= 256);
-        if (pick && fd_gemm_pp_ok(g, batch, 31)) best_tile = 31;
+        if (pick && gemm_pp_ok(g, batch, 31, 1)) best_tile = 31;
     }
+    // ---- what overrides the rule: the caller's forced tile / split and the forms that leave no choice
     if (d->tile) best_tile = d->tile;
     if (d->split_k > 0) best_split = d->split_k;
-    if (g.ln_stats) best_split = 1;   // the split-K finish kernel does not know the fold
-    if (d->ln_stats_out) {
-        // N == 320: the 256x320 tile spans the whole row and finalises (rstd, -mean rstd) itself.  Wider rows (and N == 320
-        // at row counts the 288-row tile divides better): the 160-wide tiles write raw per-n-tile partial sums
-        // [N / 160][M][2] for fd_ln_finalize_stats_f32.  fd_gemm_can_emit_row_stats tells the caller which it will be.
+    // (the split-K finish kernel knows neither the LayerNorm fold nor the statistics epilogue nor a per-batch bias)
+    if (g.ln_stats || g.ln_stats_out || g.strideBias) best_split = 1;
+    if (g.ln_stats_out) {
         int stile = 0;
         const int slabs = fd_stats_plan(g.M, g.N, &stile, batch);
-        // (batch > 1: the batches' rows must follow each other in C so that row index = batch * M + m)
-        FD_CHECK_ARG(slabs > 0 && !d->conv && !d->trans_out && !d->out_f32 &&
-                         (batch == 1 || d->batch_stride_c == (int64_t)g.M * g.ldc), FD_ESHAPE,
-                     "fd_gemm_f16: ln_stats_out needs N == 320 with M %% 256 == 0, or N %% 160 == 0 with M %% 128 == 0 or M %% 288 == 0 (got M=%d N=%d)", g.M, g.N);
-        g.ln_stats_out = d->ln_stats_out;
-        g.stats_rows = g.M * batch;
-        g.ln_eps = d->ln_eps > 0.f ? d->ln_eps : 1e-5f;
         // (a caller-forced 160-wide tile of the same row count keeps the slab layout)
         if (!(slabs > 1 && stile != 23 && (best_tile == 12 || best_tile == 20 || (best_tile == 13 && g.M % 256 == 0)))) best_tile = stile;
-        best_split = 1;
     }
-    {
-        // The many-wave tiles exist only on the LDS-DMA path, whose buffer descriptors address a
-        // tensor through 32-bit byte offsets (< 2 GiB).  Larger operands go to the register-staged
-        // 4-wave kernel (32-bit ELEMENT offsets: < 2^31 halfs = 4 GiB); beyond that, refuse.
-        const unsigned long long a_elems =
-            g.mode == MODE_CONV ? ((unsigned long long)(g.M / (g.Ho * g.Wo)) * g.Hi * g.Wi - 1) * g.Cpix + g.Cin
-                                : (unsigned long long)(g.M - 1) * g.lda + g.K;
-        const unsigned long long w_elems = (unsigned long long)(g.N - 1) * g.ldw + g.K;
-        const unsigned long long c_elems = (unsigned long long)(g.M - 1) * g.ldc + g.N;
-        FD_CHECK_ARG(a_elems < 0x7fffffffull && w_elems < 0x7fffffffull && c_elems < 0x7fffffffull, FD_ESHAPE,
-                     "fd_gemm_f16: operand of %llu elements exceeds the 2^31-element addressing limit; "
-                     "split the batch", a_elems > w_elems ? a_elems : w_elems);
-        // a per-batch bias is only staged by the LDS-DMA kernels (the global-memory fallbacks of the epilogues read bias[n])
-        FD_CHECK_ARG(g.strideBias == 0 || (batch > 1 && g.bias && g_use_dma && g.bias_lds && 2 * a_elems < 0x7fffffffull &&
-                                          2 * w_elems < 0x7fffffffull && d->split_k <= 1),
-                     FD_ESHAPE, "fd_gemm_f16: batch_stride_bias needs batch > 1, a bias, the LDS-DMA path with LDS-staged biases and no split-K");
-        if (g.strideBias) best_split = 1;
-        if (2 * a_elems >= 0x7fffffffull || 2 * w_elems >= 0x7fffffffull) {
-            // the register-staged kernel knows neither the LayerNorm fold nor the producer statistics: refuse
-            // rather than hand the consumer GEMM uninitialised statistics
-            FD_CHECK_ARG(!g.ln_stats && !g.ln_stats_out, FD_ESHAPE,
-                         "fd_gemm_f16: ln_stats / ln_stats_out need the LDS-DMA path (operands < 2 GiB); split the batch");
-            best_tile = geglu ? 1 : (g.N % 160 == 0 ? 2 : 1);   // 128x160 / 128x128, 4 waves
-            if (g.N <= 64) best_tile = 3;
-        }
+    if (!gemm_extents(g, g.mode == MODE_CONV).dma_ok()) {
+        best_tile = geglu ? 1 : (g.N % 160 == 0 ? 2 : 1);   // 128x160 / 128x128, 4 waves: the register-staged kernel
+        if (g.N <= 64) best_tile = 3;
     }
-    if (g.phase) {
-        // only the lean plain epilogue knows the parity row map: the chosen tile must have one and every tile must be full
-        int bm = 0, bn = 0;
-        switch (best_tile) {
-            case 9: case 12: case 20: bm = 128; bn = 160; break;
-            case 10: bm = 128; bn = 128; break;
-            case 13: bm = 256; bn = 160; break;
-            case 23: bm = 288; bn = 160; break;
-            case 14: bm = 256; bn = 128; break;
-            case 15: bm = 256; bn = 256; break;
-            case 16: bm = 256; bn = 320; break;
-            case 30: case 31: case 32: case 33: fd_gemm_pp_tile_shape(best_tile, &bm, &bn); break;
-            default: break;
-        }
-        FD_CHECK_ARG(bm && g.M % bm == 0 && g.N % bn == 0 && best_split == 1, FD_ESHAPE,
+    p->tile = best_tile;
+    p->split = best_split;
+}
+
+static void gemm_rule(const GemmArgs& g, const fd_gemm_desc* d, GemmPlan* p) {
+    const int form = gemm_form(g), batch = p->batch;
+    p->split = 1;
+    p->gn_parts_bm = 0;
+    // priced at the ALGORITHMIC work of the op it implements: the phase-decomposed upsample convolution (batch 4, K = 4 Cin)
+    // stands for a 3x3 convolution over the 4 M upsampled pixels (K = 9 Cin), of which it executes 4/9 of the MACs
+    p->flops_exec = 2.0 * (double)g.M * g.N * ((double)g.K + g.K2) * batch;
+    p->flops = (g.phase ? 2.25 : 1.0) * p->flops_exec;
+    if (form == FORM_TRANS_TAIL) {
+        p->tile = 9;
+        p->tag = fd_tag(14u, g.M, g.N, g.K, g.tr_n0);
+    } else if (form == FORM_SOFTMAX) {
+        p->tile = xfold_rule(d, batch);
+        p->tag = fd_tag(15u, g.M * batch, g.N, g.K, p->tile);
+    } else if (form == FORM_TRANS_OUT) {
+        // 128x160 with 8 waves where 160 | N and the rows fill the chip: -16..18 % on the 64x64 / 32x32
+        // self-attention V projections (tools/ab_vt.py; 256x160 / 16 waves is no better, 16x16 maps tie).
+        // FD_GEMM_VT_TILE=0: the 128x64 / 4-wave tile everywhere (A/B)
+        static const int vt_tile = getenv("FD_GEMM_VT_TILE") ? atoi(getenv("FD_GEMM_VT_TILE")) : 9;
+        const bool vt160 = vt_tile && g.N % 160 == 0 && batch == 1 && g.M >= 8192 && GemmExtents::below_2gib(gemm_extents(g, false).a);
+        p->tile = vt160 ? 9 : 3;      // (the transposed-store forms of the 128x160 / 128x64 tiles)
+        p->tag = fd_tag(10u, g.M, g.N, g.K, p->tile);
+    } else {
+        gemm_rule_tile(g, d, p);
+        // (the 160- and 320-wide 2-barrier tiles have no GEGLU epilogue: value and gate columns would fall into different waves)
+        if (g.act == FD_ACT_GEGLU && (p->tile == 2 || p->tile == 5 || p->tile == 7 || p->tile == 9 || p->tile == 12 || p->tile == 13 || p->tile == 16 || p->tile == 20 || p->tile == 23)) p->tile = 1;
+        // small problems under the LayerNorm fold: the generic epilogue with the fold compiled in, 64x64 for few rows, else 128x128 (reported as -7)
+        if (g.ln_stats && !gemm_tile_ln_fold(p->tile)) p->tile = p->tile == 4 ? 4 : -7;
+        p->gn_parts_bm = gn_parts_bm(g, p->tile, p->split, batch, d->gn_groups);
+        p->tag = fd_tag(11u, g.M * batch, g.N, g.K + g.K2, p->tile * 64 + p->split, (g.mode << 8) | (g.act << 4) | (g.res ? 2 : 0) | (g.ln_stats ? 1 : 0));
+    }
+}
+
+// The checks that need the chosen tile, between the rule and the launch
+static int gemm_check_tile(const GemmArgs& g, const fd_gemm_desc* d, const GemmPlan& p) {
+    // (the forms with a fixed kernel have none of these: no phase, no residual_rows, no split, no ping-pong tile)
+    int bm, bn;
+    gemm_tile_shape(p.tile, &bm, &bn);
+    if (g.phase)
+        // only the lean plain epilogue knows the parity row map: the chosen tile must have one (26 has statistics epilogues only) and every tile must be full
+        FD_CHECK_ARG(bm && p.tile != 26 && g.M % bm == 0 && g.N % bn == 0 && p.split == 1, FD_ESHAPE,
                      "fd_gemm_f16: upsample2x == 2: tile %d / split %d cannot run M=%d N=%d through the lean epilogue",
-                     best_tile, best_split, g.M, g.N);
-    }
+                     p.tile, p.split, g.M, g.N);
     if (g.res_rows) {
         // the lean epilogues wrap the residual row once per wave row block: a tile must not straddle the wrap (the finish pass of a launch split
-        // over K adds the residual and wraps per row)
-        const int bm = best_tile == 23 ? 288 : 256;
-        FD_CHECK_ARG(best_split > 1 || g.res_rows % bm == 0, FD_ESHAPE,
-                     "fd_gemm_f16: residual_rows=%d with tile %d (needs a multiple of %d rows)", g.res_rows, best_tile, bm);
+        // over K adds the residual and wraps per row).  256 rows cover every tile but the 288-row one.
+        const int rows = bm > 256 ? bm : 256;
+        FD_CHECK_ARG(p.split > 1 || g.res_rows % rows == 0, FD_ESHAPE,
+                     "fd_gemm_f16: residual_rows=%d with tile %d (needs a multiple of %d rows)", g.res_rows, p.tile, rows);
     }
-    if (best_split > 1)
-        FD_CHECK_ARG(!geglu && batch == 1 && g.N % 4 == 0 && g.ws &&
-                         (size_t)best_split * g.M * g.N * 4 <= (size_t)d->workspace_bytes,
-                     FD_ESHAPE, "fd_gemm_f16: split_k=%d not possible for this problem", best_split);
-    if (geglu && (best_tile == 2 || best_tile == 5 || best_tile == 7 || best_tile == 9 || best_tile == 12 || best_tile == 13 || best_tile == 16 || best_tile == 20 || best_tile == 23)) best_tile = 1;
-    g.split_k = best_split;
-    g.tap_fast = g.mode == MODE_CONV && (g_tap_fast == 2 || (g_tap_fast == 1 && best_tile == 16) || best_tile >= 30);   // (the ping-pong tiles are tap-fastest only)
-    if (best_tile >= 30)
-        FD_CHECK_ARG(fd_gemm_pp_ok(g, batch, best_tile), FD_ESHAPE,
+    if (p.split > 1)
+        FD_CHECK_ARG(g.act != FD_ACT_GEGLU && p.batch == 1 && g.N % 4 == 0 && g.ws &&
+                         (size_t)p.split * g.M * g.N * 4 <= (size_t)d->workspace_bytes,
+                     FD_ESHAPE, "fd_gemm_f16: split_k=%d not possible for this problem", p.split);
+    if (p.tile >= 30)
+        FD_CHECK_ARG(gemm_pp_ok(g, p.batch, p.tile, p.split), FD_ESHAPE,
                      "fd_gemm_f16: ping-pong tile %d cannot run M=%d N=%d K=%d (full tiles, K %% 64 == 0, conv: Wo %% 8 == 0, no fused upsample)",
-                     best_tile, g.M, g.N, g.K);
-    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile == 26 || best_tile >= 30))
-        best_tile = best_tile == 4 ? 4 : -7;     // (reported by fd_gemm_plan as -7: the 128x128 generic kernel with the fold compiled in)
-    if (choice) {
-        if (choice[0] == -1) choice[2] = gn_parts_bm(g, best_tile, best_split, batch);   // fd_gemm_gn_parts_chunks
-        choice[0] = best_tile;
-        choice[1] = best_split;
-        return FD_OK;
-    }
+                     p.tile, g.M, g.N, g.K);
+    return FD_OK;
+}
+
+// Stages 1 and 2 with the checks between them: what fd_gemm_plan answers and fd_gemm_f16 launches
+static int gemm_prepare(const fd_gemm_desc* d, GemmArgs& g, GemmPlan* p) {
+    const int rc = gemm_check(d, g, &p->batch);
+    if (rc != FD_OK) return rc;
+    gemm_rule(g, d, p);
+    return gemm_check_tile(g, d, *p);
+}
+
+// What only a launch is refused for: fd_gemm_plan answers these descriptors (the Python front asks it for the split of a gn_out launch)
+static int gemm_check_launch(const fd_gemm_desc* d, const GemmArgs& g, const GemmPlan& p) {
+    if (gemm_form(g) != FORM_RULE) return FD_OK;
     if (g.gn_part_out)
-        FD_CHECK_ARG(gn_parts_bm(g, best_tile, best_split, batch) > 0 && (uintptr_t)g.gn_part_out % 8 == 0 &&
-                         g.rows_per_batch / gn_parts_bm(g, best_tile, best_split, batch) == d->gn_part_chunks, FD_ESHAPE,
+        FD_CHECK_ARG(p.gn_parts_bm > 0 && (uintptr_t)g.gn_part_out % 8 == 0 && g.rows_per_batch / p.gn_parts_bm == d->gn_part_chunks, FD_ESHAPE,
                      "fd_gemm_f16: gn_part_out cannot be honoured by tile %d x split %d of M=%d N=%d (rows per sample %d, %d groups); ask fd_gemm_gn_parts_chunks first",
-                     best_tile, best_split, g.M, g.N, g.rows_per_batch, g.gn_groups);
+                     p.tile, p.split, g.M, g.N, g.rows_per_batch, g.gn_groups);
     if (g.gn_out)
-        FD_CHECK_ARG(best_split == 2 || best_split == 4 || best_split == 8 || best_split == 16, FD_ESHAPE,
-                     "fd_gemm_f16: gn_out is honoured by split-K launches only (this one: tile %d, split_k %d); ask fd_gemm_plan first", best_tile, best_split);
-    fd_prof_begin(FD_FAMILY_GEMM, st, flops, flops_exec, fd_tag(11u, g.M * batch, g.N, g.K + g.K2, best_tile * 64 + best_split, (g.mode << 8) | (g.act << 4) | (g.res ? 2 : 0) | (g.ln_stats ? 1 : 0)));
-    if (g.ln_stats && !(best_tile == 9 || best_tile == 10 || (best_tile >= 12 && best_tile <= 16) || best_tile == 20 || best_tile == 23 || best_tile == 26 || best_tile >= 30)) {
-        // small problems: the generic epilogue with the fold compiled in (64x64 for few rows)
-        rc = best_tile == 4 ? launch_mode<64, 64, false, false, 2, 2, 2, 7>(g, batch, st)
-                            : launch_mode<128, 128, false, false, 2, 2, 2, 7>(g, batch, st);
-        fd_prof_end(FD_FAMILY_GEMM, st);
-        return rc;
-    }
-    if (best_tile == 26) {   // 64 rows per launch slice (gemm_xfold.h)
-        rc = xfold_launch_out64(g, batch, st);
-        fd_prof_end(FD_FAMILY_GEMM, st);
-        return rc;
-    }
+        FD_CHECK_ARG(p.split == 2 || p.split == 4 || p.split == 8 || p.split == 16, FD_ESHAPE,
+                     "fd_gemm_f16: gn_out is honoured by split-K launches only (this one: tile %d, split_k %d); ask fd_gemm_plan first", p.tile, p.split);
+    return FD_OK;
+}
+
+// Stage 3, the forms with a fixed kernel: the transposed tail, the per-head softmax (gemm_xfold.h) and the transposed store
+static int gemm_launch_form(GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    const int form = gemm_form(g), batch = p.batch;
+    if (form == FORM_TRANS_TAIL) return launch_mode<128, 160, false, false, 4, 2, 2, 13>(g, 1, st);
+    if (form == FORM_SOFTMAX) return xfold_launch_probs(g, batch, p.tile, st);
+    if (p.tile == 9)
+        return g.ln_stats ? launch_mode<128, 160, true, false, 4, 2, 2, 7>(g, batch, st) : launch_mode<128, 160, true, false, 4, 2, 2, 0>(g, batch, st);
+    return g.ln_stats ? launch_mode<128, 64, true, false, 2, 2, 2, 7>(g, batch, st) : launch<128, 64, true>(g, batch, st);
+}
+
+// Stage 3, the rule's form: the tile's kernel and, for a launch split over K, the finish kernel
+static int gemm_launch_tile(GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    const int best_tile = p.tile, batch = p.batch;
+    g.split_k = p.split;
+    g.tap_fast = g.mode == MODE_CONV && (g_tap_fast == 2 || (g_tap_fast == 1 && best_tile == 16) || best_tile >= 30);   // (the ping-pong tiles are tap-fastest only)
+    if (g.ln_stats && !gemm_tile_ln_fold(best_tile))   // (the rule left 4 or -7)
+        return best_tile == 4 ? launch_mode<64, 64, false, false, 2, 2, 2, 7>(g, batch, st) : launch_mode<128, 128, false, false, 2, 2, 2, 7>(g, batch, st);
+    if (best_tile == 26) return xfold_launch_out64(g, batch, st);   // 64 rows per launch slice (gemm_xfold.h)
+    int rc;
     switch (best_tile) {
         case 2: rc = launch<128, 160, false>(g, batch, st); break;
         case 3: rc = launch<128, 64, false>(g, batch, st); break;
@@ -1763,6 +1776,45 @@ static int gemm_impl(const fd_gemm_desc* d, void* stream, int* choice) {
         hipLaunchKernelGGL(k_splitk_finish, dim3(blocks), dim3(256), 0, st, g);
         FD_CHECK_LAUNCH("k_splitk_finish");
     }
+    return rc;
+}
+
+// Stage 3: the launch of a planned descriptor inside its profile bracket
+static int gemm_launch(GemmArgs& g, const GemmPlan& p, hipStream_t st) {
+    fd_prof_begin(FD_FAMILY_GEMM, st, p.flops, p.flops_exec, p.tag);
+    const int rc = gemm_form(g) == FORM_RULE ? gemm_launch_tile(g, p, st) : gemm_launch_form(g, p, st);
     fd_prof_end(FD_FAMILY_GEMM, st);
     return rc;
+}
+
+extern "C" int fd_gemm_f16(const fd_gemm_desc* d, void* stream) {
+    if (fd_plan_recording() && d) {
+        const fd_gemm_desc dc_ = *d;
+        fd_plan_push([dc_](void* fd_s_) -> int { return fd_gemm_f16(&dc_, fd_s_); });
+    }
+    GemmArgs g;
+    GemmPlan p;
+    int rc = gemm_prepare(d, g, &p);
+    if (rc == FD_OK) rc = gemm_check_launch(d, g, p);
+    return rc == FD_OK ? gemm_launch(g, p, (hipStream_t)stream) : rc;
+}
+
+// The tile id and split-K factor fd_gemm_f16 would launch `d` with (after the same argument checks), without launching anything:
+// host logic only, no HIP call -- usable without a device (tests/test_gemm_rule_table.py pins the rule's choices on the launches
+// of the bench forward).  Pointers are only tested for NULL / alignment.
+extern "C" int fd_gemm_plan(const fd_gemm_desc* d, int* tile, int* split_k) {
+    FD_CHECK_ARG(tile && split_k, FD_EINVAL, "fd_gemm_plan: null output pointer");
+    GemmArgs g;
+    GemmPlan p;
+    const int rc = gemm_prepare(d, g, &p);
+    *tile = rc == FD_OK ? p.tile : 0;
+    *split_k = rc == FD_OK ? p.split : 0;
+    return rc;
+}
+
+extern "C" int fd_gemm_gn_parts_chunks(const fd_gemm_desc* d) {
+    GemmArgs g;
+    GemmPlan p;
+    if (!d || gemm_prepare(d, g, &p) != FD_OK || p.gn_parts_bm <= 0) return 0;
+    return g.rows_per_batch / p.gn_parts_bm;
 }

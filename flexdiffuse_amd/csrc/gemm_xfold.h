@@ -8,9 +8,8 @@
 #pragma once
 
 
-static int xfold_probs_impl(const fd_gemm_desc* d, GemmArgs& g, int batch, void* stream, int* choice) {
-    // per-head softmax of the output columns (see the header): launch 1 of the context-folded cross-attention.  Everything the form
-    // cannot run is refused here -- the caller asks fd_gemm_plan first and keeps its unfolded launches for a refused shape
+// Everything the softmax form cannot run is refused here -- the caller asks fd_gemm_plan first and keeps its unfolded launches for a refused shape
+static int xfold_check(const fd_gemm_desc* d, GemmArgs& g, int batch) {
     FD_CHECK_ARG(d->ln_stats && !d->conv && !d->trans_out && d->act == FD_ACT_NONE && !d->residual && !d->out_f32 && !d->K2 && !d->ln_stats_out &&
                      !d->gn_out && !d->gn_part_out && !d->trans_n0 && !d->residual_rows && d->split_k <= 1,
                  FD_EINVAL, "fd_gemm_f16: softmax_group needs a plain LayerNorm-fold linear GEMM (ln_stats; act NONE, fp16 output, no residual / appended operand / "
@@ -22,29 +21,23 @@ static int xfold_probs_impl(const fd_gemm_desc* d, GemmArgs& g, int batch, void*
     FD_CHECK_ARG(d->M % 64 == 0, FD_ESHAPE, "fd_gemm_f16: softmax_group: M=%d rows per launch slice is not a multiple of the 64-row tile (a tile would straddle two samples)", d->M);
     FD_CHECK_ARG(batch == 1 || (d->bias && d->batch_stride_c == (int64_t)d->M * d->ldc), FD_ESHAPE,
                  "fd_gemm_f16: softmax_group with batch > 1 needs a bias and batch_stride_c == M * ldc");
-    const unsigned long long ab = 2ull * ((unsigned long long)(d->M - 1) * d->lda + d->K), wb = 2ull * ((unsigned long long)(d->N - 1) * d->ldw + d->K);
-    const unsigned long long cb = 2ull * ((unsigned long long)(d->M - 1) * d->ldc + d->N);
-    FD_CHECK_ARG(ab < 0x7fffffffull && wb < 0x7fffffffull && cb < 0x7fffffffull, FD_ESHAPE, "fd_gemm_f16: softmax_group: operands >= 2 GiB");
-    FD_CHECK_ARG(g_use_dma && g_fast_epi && g_bias_lds, FD_ESHAPE, "fd_gemm_f16: softmax_group needs the LDS-DMA path with the lean epilogue and LDS-staged biases");
-    // 24: 64 x 160, 4 waves; 25: 128 x 160, 8 waves (both 32x80 wave tiles, 3 LDS stages).  The 128-row tile from 128 workgroups on: at the 16x16 level
-    // of the bench forward (16 x 256 rows, 128 against 256 workgroups) it takes 19.8 us against 22.5 us (tools/ab_xattn_fold.py)
-    int stile = (d->M % 128 == 0 && (long long)(d->M / 128) * (d->N / 160) * batch >= 128) ? 25 : 24;
-    if (d->tile == 24 || (d->tile == 25 && d->M % 128 == 0)) stile = d->tile;
-    else FD_CHECK_ARG(d->tile == 0, FD_ESHAPE, "fd_gemm_f16: softmax_group runs on tile 24 (64x160) or 25 (128x160, M %% 128 == 0), not %d", d->tile);
+    const GemmExtents ext = gemm_extents(g, false);
+    FD_CHECK_ARG(ext.dma_ok() && GemmExtents::below_2gib(ext.c), FD_ESHAPE, "fd_gemm_f16: softmax_group: operands >= 2 GiB");
+    FD_CHECK_ARG(gemm_lean_dma_path(), FD_ESHAPE, "fd_gemm_f16: softmax_group needs the LDS-DMA path with the lean epilogue and LDS-staged biases");
+    FD_CHECK_ARG(d->tile == 0 || d->tile == 24 || (d->tile == 25 && d->M % 128 == 0), FD_ESHAPE,
+                 "fd_gemm_f16: softmax_group runs on tile 24 (64x160) or 25 (128x160, M %% 128 == 0), not %d", d->tile);
     g.sm_valid = d->softmax_valid;
-    g.split_k = 1;
-    g.bias_lds = g_bias_lds;
-    if (choice) {
-        choice[0] = stile;
-        choice[1] = 1;
-        return FD_OK;
-    }
-    hipStream_t st2 = (hipStream_t)stream;
-    const double fl = 2.0 * (double)d->M * d->N * d->K * batch;
-    fd_prof_begin(FD_FAMILY_GEMM, st2, fl, fl, fd_tag(15u, g.M * batch, g.N, g.K, stile));
-    const int rc2 = stile == 25 ? launch_mode<128, 160, false, false, 4, 3, 2, 14>(g, batch, st2) : launch_mode<64, 160, false, false, 2, 3, 2, 14>(g, batch, st2);
-    fd_prof_end(FD_FAMILY_GEMM, st2);
-    return rc2;
+    return FD_OK;
+}
+
+// 24: 64 x 160, 4 waves; 25: 128 x 160, 8 waves (both 32x80 wave tiles, 3 LDS stages).  The 128-row tile from 128 workgroups on: at the 16x16 level
+// of the bench forward (16 x 256 rows, 128 against 256 workgroups) it takes 19.8 us against 22.5 us (tools/ab_xattn_fold.py)
+static int xfold_rule(const fd_gemm_desc* d, int batch) {
+    return d->tile ? d->tile : ((d->M % 128 == 0 && (long long)(d->M / 128) * (d->N / 160) * batch >= 128) ? 25 : 24);
+}
+
+static int xfold_launch_probs(GemmArgs& g, int batch, int stile, hipStream_t st2) {
+    return stile == 25 ? launch_mode<128, 160, false, false, 4, 3, 2, 14>(g, batch, st2) : launch_mode<64, 160, false, false, 2, 3, 2, 14>(g, batch, st2);
 }
 
 // tile 26: 64 x 160, 4 waves, 32x80 wave tiles, statistics (+ residual) epilogue only (fd_stats_plan picks it for batched launches of 64 rows)

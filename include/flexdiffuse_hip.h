@@ -230,7 +230,8 @@ typedef struct fd_gemm_desc {
      * at the 16x16 / 8x8 levels, where the convolution is split over K, the pass that sums the fp32 partial slabs normalises the
      * tile it has just summed -- one launch less, and with gn_skip_c the convolution's own output never goes to HBM (C may then be
      * NULL).  Only honoured by split-K launches (ask fd_gemm_plan for the split, fd_gemm_can_fuse_groupnorm for the shape);
-     * FD_ESHAPE otherwise.  act NONE, fp16 output, batch 1; residual row stride % 8 == 0.  NULL = off. */
+     * FD_ESHAPE otherwise.  act NONE, fp16 output, batch 1; residual row stride % 8 == 0; not together with residual_rows (FD_EINVAL:
+     * this finish pass adds residual row m, it does not wrap).  NULL = off. */
     void* gn_out;
     const float* gn_gamma; /* [N] */
     const float* gn_beta;  /* [N] */
@@ -274,7 +275,8 @@ typedef struct fd_gemm_desc {
     /* (ABI 12) residual_rows > 0: output row m adds residual row m %% residual_rows -- the residual of a GEMM whose rows are `rep` replicas of
      * a shared prefix (the classifier-free-guidance fan-out inside `unet(...)`, reference pipeline/guide.py:56-58: both halves of the batch read
      * the same hidden states until the first cross-attention) without materialising the replicas.  Linear GEMM, batch 1,
-     * M %% residual_rows == 0 and residual_rows a multiple of the tile's rows (256 covers every tile but the 288-row one).  0 = row m. */
+     * M %% residual_rows == 0 and residual_rows a multiple of the tile's rows (256 covers every tile but the 288-row one).  Not together
+     * with gn_out (FD_EINVAL: the GroupNorm finish pass does not wrap the residual rows).  0 = row m. */
     int32_t residual_rows;
     /* (additive; FD_ABI_VERSION stays 12) PER-HEAD SOFTMAX of the output: the N columns are `N / softmax_group` groups of softmax_group = 80
      * base-2 logits, of which the first softmax_valid (1..80) are real keys; C[m][group] = softmax over those, stored normalised fp16, the pad

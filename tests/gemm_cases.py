@@ -179,7 +179,7 @@ def launch_epi(g, split, env, BM, BN, WM, NS, WN, ALLOW):
 
 
 def select(g, tile, split, env={}) -> Launch:
-    '''What gemm_impl launches for the (already planned) tile id and split factor: the part of fd_gemm_f16 behind the rule.  `g` carries
+    '''What gemm_launch launches for the (already planned) tile id and split factor: the part of fd_gemm_f16 behind the rule.  `g` carries
     M, N, K, K2, act, res, ldr, ldc, bias, bias2, rows, out_f32, trans, trans_n0, conv, ln, ln_parts, stats_out, gn_part, gn_out, stride_bias, batch.'''
     dma = 'FD_GEMM_NO_DMA' not in env
     lean_ok = dma and int(env.get('FD_GEMM_FAST_EPI', 1)) != 0 and int(env.get('FD_GEMM_BIAS_LDS', 1)) != 0
