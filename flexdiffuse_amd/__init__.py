@@ -13,7 +13,7 @@ Tweener = _guidance.Tweener
 preprocess = _encode.preprocess
 FlexPipeline = _flex.FlexPipeline
 
-from .pipeline.guide import GuideBase, PromptGuide, ScheduledGuide, SimpleGuide  # noqa: E402,F401
+from .pipeline.guide import GuideBase, PromptGuide, ScheduledGuide, SimpleGuide, WindowedGuide  # noqa: E402,F401
 from .noise import PhiloxNoise  # noqa: E402,F401
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler,  # noqa: E402,F401
                         LMSDiscreteScheduler, PNDMScheduler)

@@ -1,0 +1,186 @@
+// Windowed (MultiDiffusion, Bar-Tal et al. 2023) sampling on the device loop: a canvas latent of any size is covered by
+// overlapping windows of the model's own size, the UNet runs on all windows as one batch, and the guided predictions are
+// averaged where windows overlap before ONE scheduler step on the canvas.
+//   fd_window_gather_f32   canvas (B, C, H, W) -> window batch (B Wn, C, h, w), before the first step and after a blend
+//   fd_window_step_f32     one launch per step after the UNet: CFG per window, the average over the covering windows
+//                          (-> eps_out), the DDIM (eta = 0) update of the canvas and the next step's window batch
+// The grid travels as plain ints (H, W, h, w, stride_y, stride_x, ny, nx): along an axis of extent S with windows of
+// extent s and stride d there are n = ceil((S - s) / d) + 1 windows at offsets o_i = min(i d, S - s) -- the last one
+// snapped to the edge.  Window (iy, ix) is w = iy nx + ix; sample b, window w is row b Wn + w of the UNet batch.
+// Every operation is one of latent_step.h or a separately rounded fp32 intrinsic, in the order written in
+// include/flexdiffuse_hip.h, so the step is bit-equal to an fp32 torch restatement and, on a one-window grid, to
+// fd_cfg_ddim_step_f32.
+#include "latent_step.h"
+
+enum { FD_WINDOW_MAX = 16, FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
+
+struct FdWindowGrid {
+    int H, W, h, w, sy, sx, ny, nx;
+};
+
+__host__ __device__ __forceinline__ int fd_window_offset(int i, int d, int S, int s) {
+    const int o = i * d;
+    return o < S - s ? o : S - s;
+}
+
+// One thread owns one element of the window batch: the stores are contiguous, the loads contiguous along a window row.
+__global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ canvas, float* __restrict__ windows,
+                                                       int B, int C, const FdWindowGrid g) {
+    const int Wn = g.ny * g.nx;
+    const size_t total = (size_t)B * Wn * C * g.h * g.w;
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int lx = e % g.w;
+        size_t r = e / g.w;
+        const int ly = r % g.h;
+        r /= g.h;
+        const int c = r % C;
+        r /= C;
+        const int wi = r % Wn;
+        const int b = r / Wn;
+        const int y = fd_window_offset(wi / g.nx, g.sy, g.H, g.h) + ly;
+        const int x = fd_window_offset(wi % g.nx, g.sx, g.W, g.w) + lx;
+        windows[e] = canvas[(((size_t)b * C + c) * g.H + y) * g.W + x];
+    }
+}
+
+// One thread owns one canvas cell (b, y, x) and all C channels; consecutive threads run along x, so every NCHW plane is
+// written in whole rows.  V = 4: float4 loads along the channels of the eps rows (C % 4 == 0, ld % 4 == 0, 16-byte base).
+template <int V>
+__global__ __launch_bounds__(256) void k_window_step(float* __restrict__ x, float* __restrict__ wout,
+                                                     const float* __restrict__ eps, float* __restrict__ eps_out, int B,
+                                                     int C, int ld, const FdWindowGrid g, int tent, int cfg, float gscale,
+                                                     float c1, float c2, float c3, float c4, int vpred, int do_step) {
+    const int Wn = g.ny * g.nx, hw = g.h * g.w;
+    const size_t HW = (size_t)g.H * g.W;
+    const size_t total = (size_t)B * HW;
+    const size_t half = (size_t)B * Wn * hw * ld;        // the conditional rows follow the unconditional ones
+    for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
+        const int px = e % g.W;
+        const int py = (e / g.W) % g.H;
+        const int b = e / HW;
+        for (int c0 = 0; c0 < C; c0 += V) {
+            float acc[V], last[V], u[V], t[V];
+#pragma unroll
+            for (int j = 0; j < V; ++j) acc[j] = 0.f;
+            float wsum = 0.f;
+            int count = 0;
+            for (int iy = 0; iy < g.ny; ++iy) {
+                const int ly = py - fd_window_offset(iy, g.sy, g.H, g.h);
+                if (ly < 0 || ly >= g.h) continue;
+                for (int ix = 0; ix < g.nx; ++ix) {
+                    const int lx = px - fd_window_offset(ix, g.sx, g.W, g.w);
+                    if (lx < 0 || lx >= g.w) continue;
+                    const size_t row = (((size_t)b * Wn + iy * g.nx + ix) * hw + (size_t)ly * g.w + lx) * ld + c0;
+                    if (cfg) {
+                        fd_ldv<V>(eps + row, u);
+                        fd_ldv<V>(eps + half + row, t);
+#pragma unroll
+                        for (int j = 0; j < V; ++j) last[j] = fd_cfg_mix(u[j], t[j], gscale);
+                    } else {
+                        fd_ldv<V>(eps + row, last);
+                    }
+                    if (tent) {
+                        const float wgt = (float)(min(ly + 1, g.h - ly) * min(lx + 1, g.w - lx));
+#pragma unroll
+                        for (int j = 0; j < V; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(wgt, last[j]));
+                        wsum = __fadd_rn(wsum, wgt);
+                    } else {
+#pragma unroll
+                        for (int j = 0; j < V; ++j) acc[j] = __fadd_rn(acc[j], last[j]);
+                    }
+                    ++count;
+                }
+            }
+            // the exact branch is part of the contract: (w g) / w is not g in fp32
+            const float den = tent ? wsum : (float)count;
+#pragma unroll
+            for (int j = 0; j < V; ++j) {
+                float v = count == 1 ? last[j] : __fdiv_rn(acc[j], den);
+                const size_t o = ((size_t)b * C + c0 + j) * HW + (size_t)py * g.W + px;     // NCHW canvas
+                if (eps_out) eps_out[o] = v;
+                if (do_step) {
+                    v = fd_ddim_update(x[o], v, c1, c2, c3, c4, vpred);
+                    x[o] = v;
+                }
+                last[j] = v;
+            }
+            if (!wout) continue;
+            // the next UNet input: this cell of every covering window has exactly this one source
+            for (int iy = 0; iy < g.ny; ++iy) {
+                const int ly = py - fd_window_offset(iy, g.sy, g.H, g.h);
+                if (ly < 0 || ly >= g.h) continue;
+                for (int ix = 0; ix < g.nx; ++ix) {
+                    const int lx = px - fd_window_offset(ix, g.sx, g.W, g.w);
+                    if (lx < 0 || lx >= g.w) continue;
+                    float* dst = wout + (((size_t)b * Wn + iy * g.nx + ix) * C + c0) * hw + (size_t)ly * g.w + lx;
+#pragma unroll
+                    for (int j = 0; j < V; ++j) dst[(size_t)j * hw] = last[j];
+                }
+            }
+        }
+    }
+}
+
+// the checks the two entry points share: the grid's own rule, restated on the host
+static int fd_window_grid_args(const char* who, int B, int C, const FdWindowGrid& g) {
+    FD_CHECK_ARG(B > 0 && C > 0 && g.h > 0 && g.w > 0, FD_EINVAL, "%s: sizes", who);
+    FD_CHECK_ARG(g.h <= g.H && g.w <= g.W, FD_EINVAL, "%s: the window (%d, %d) is larger than the canvas (%d, %d)", who,
+                 g.h, g.w, g.H, g.W);
+    FD_CHECK_ARG(g.sy >= 1 && g.sy <= g.h && g.sx >= 1 && g.sx <= g.w, FD_EINVAL,
+                 "%s: the stride (%d, %d) is outside [1, window]: windows would leave gaps", who, g.sy, g.sx);
+    FD_CHECK_ARG(g.ny >= 1 && g.nx >= 1 && g.ny <= FD_WINDOW_MAX && g.nx <= FD_WINDOW_MAX, FD_EINVAL,
+                 "%s: %d x %d windows: more than %d on an axis", who, g.ny, g.nx, (int)FD_WINDOW_MAX);
+    FD_CHECK_ARG(g.ny == (g.H - g.h + g.sy - 1) / g.sy + 1 && g.nx == (g.W - g.w + g.sx - 1) / g.sx + 1, FD_EINVAL,
+                 "%s: %d x %d windows do not match the count rule ceil((S - s) / d) + 1", who, g.ny, g.nx);
+    FD_CHECK_ARG((unsigned long long)B * g.ny * g.nx * g.h * g.w <= 0x7fffffffull &&
+                     (unsigned long long)g.H * g.W <= 0x7fffffffull, FD_EINVAL, "%s: sizes: cells past 2^31", who);
+    return FD_OK;
+}
+
+extern "C" int fd_window_gather_f32(const float* canvas, float* windows, int B, int C, int H, int W, int h, int w,
+                                    int stride_y, int stride_x, int ny, int nx, void* stream) {
+    FD_PLAN(fd_window_gather_f32(canvas, windows, B, C, H, W, h, w, stride_y, stride_x, ny, nx, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(canvas && windows, FD_EINVAL, "fd_window_gather_f32: canvas or windows is null");
+    const FdWindowGrid g = {H, W, h, w, stride_y, stride_x, ny, nx};
+    const int rc = fd_window_grid_args("fd_window_gather_f32", B, C, g);
+    if (rc != FD_OK) return rc;
+    FD_CHECK_ARG(canvas != windows, FD_EINVAL, "fd_window_gather_f32: windows aliases the canvas");
+    const size_t total = (size_t)B * ny * nx * C * h * w;
+    hipLaunchKernelGGL(k_window_gather, dim3(fd_grid1d(total, 2048)), dim3(256), 0, (hipStream_t)stream, canvas, windows,
+                       B, C, g);
+    FD_CHECK_LAUNCH("k_window_gather");
+    return FD_OK;
+}
+
+extern "C" int fd_window_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, int B, int C, int ld,
+                                  int H, int W, int h, int w, int stride_y, int stride_x, int ny, int nx, int blend,
+                                  int cfg, float guidance, float c1, float c2, float c3, float c4, int v_prediction,
+                                  int do_step, void* stream) {
+    FD_PLAN(fd_window_step_f32(x, windows_out, eps_nhwc, eps_out, B, C, ld, H, W, h, w, stride_y, stride_x, ny, nx, blend,
+                               cfg, guidance, c1, c2, c3, c4, v_prediction, do_step, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(eps_nhwc, FD_EINVAL, "fd_window_step_f32: eps_nhwc is null");
+    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_window_step_f32: x is null");
+    FD_CHECK_ARG(do_step || (eps_out && !windows_out), FD_EINVAL,
+                 "fd_window_step_f32: the combine-only form needs eps_out (null) and writes no windows");
+    const FdWindowGrid g = {H, W, h, w, stride_y, stride_x, ny, nx};
+    const int rc = fd_window_grid_args("fd_window_step_f32", B, C, g);
+    if (rc != FD_OK) return rc;
+    FD_CHECK_ARG(ld >= C, FD_EINVAL, "fd_window_step_f32: sizes: ld %d < C %d", ld, C);
+    FD_CHECK_ARG(blend == FD_BLEND_UNIFORM || blend == FD_BLEND_TENT, FD_EINVAL,
+                 "fd_window_step_f32: blend %d is neither uniform (0) nor tent (1)", blend);
+    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "fd_window_step_f32: eps_out aliases the canvas");
+    FD_CHECK_ARG(!windows_out || (windows_out != x && windows_out != eps_out), FD_EINVAL,
+                 "fd_window_step_f32: windows_out aliases the canvas or eps_out");
+    const int blocks = fd_grid1d((size_t)B * H * W, 2048);
+    const bool vec = C % 4 == 0 && ld % 4 == 0 && (uintptr_t)eps_nhwc % 16 == 0;
+    if (vec)
+        hipLaunchKernelGGL(k_window_step<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, windows_out, eps_nhwc,
+                           eps_out, B, C, ld, g, blend, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
+    else
+        hipLaunchKernelGGL(k_window_step<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, windows_out, eps_nhwc,
+                           eps_out, B, C, ld, g, blend, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
+    FD_CHECK_LAUNCH("k_window_step");
+    return FD_OK;
+}

@@ -105,6 +105,8 @@ _SIGNATURES = {
                                                   c_uint64, c_int64, c_int, P]),
     'fd_lerp_f16': (c_int, [P, P, P, c_int64, c_float, P]),
     'fd_xattn_fold_rows_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
+    'fd_window_gather_f32': (c_int, [P, P] + [c_int] * 10 + [P]),
+    'fd_window_step_f32': (c_int, [P, P, P, P] + [c_int] * 13 + [c_float] * 5 + [c_int, c_int, P]),
     'fd_cast_f32_to_f16': (c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

@@ -1227,6 +1227,31 @@ def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: O
              float(coef[3]), int(v_prediction), int(do_step), hip.stream())
 
 
+def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, grid):
+    '''Canvas (B, C, H, W) -> window batch (B Wn, C, h, w), both NCHW fp32 (fd_window_gather_f32).  grid: the plain ints
+    (H, W, h, w, stride_y, stride_x, ny, nx) of `windows.WindowGrid.args`; the kernel restates the offsets.'''
+    H, W, h, w, _, _, ny, nx = grid
+    _check_f32(B * C * H * W, canvas)
+    _check_f32(B * ny * nx * C * h * w, windows)
+    hip.call('fd_window_gather_f32', canvas.data_ptr(), windows.data_ptr(), B, C, *(int(v) for v in grid), hip.stream())
+
+
+def window_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, grid,
+                blend: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
+                do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
+    '''Windowed step (fd_window_step_f32): eps_nhwc [(cfg + 1) * B Wn * h w][ld] fp32, the UNet output over the window batch
+    -> per canvas cell the CFG combine of every covering window, their average (blend 0: uniform, 1: tent) -> eps_out (NCHW
+    fp32, optional), with do_step the DDIM update of the canvas x (NCHW fp32, in place) and, given windows_out
+    (B Wn, C, h, w), the next step's window batch.'''
+    H, W, h, w, _, _, ny, nx = grid
+    _check_f32(B * C * H * W, x, eps_out)
+    _check_f32(B * ny * nx * C * h * w, windows_out)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * ny * nx * h * w, C)
+    hip.call('fd_window_step_f32', _p(x), _p(windows_out), eps_nhwc.data_ptr(), _p(eps_out), B, C, eps_nhwc.stride(0),
+             *(int(v) for v in grid), int(blend), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
+             float(coef[3]), int(v_prediction), int(do_step), hip.stream())
+
+
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
           exp_half_x: bool = False) -> torch.Tensor:
     assert x.dtype == torch.float32 and (y is None or (y.dtype == torch.float32 and y.numel() == x.numel())), \

@@ -40,6 +40,13 @@ scaled by a factor from two of its standard deviations, inside the step's own la
 fd_cfg_rescale_multistep_step_f32) on the fused loops and by the combine-only form of the first on the planned and generic
 routes -- the same bits on every route.  With 0 every route makes the calls it made before.
 
+Windowed sampling (`WindowedGuide`, beyond the reference; MultiDiffusion, Bar-Tal et al. 2023; windows.py): a canvas larger than
+the model's size is covered by overlapping windows, the UNet runs on all of them as one batch -- the loop's persistent buffer,
+through the graph / plan -- and one fd_window_step_f32 per step combines, averages, takes the DDIM step on the canvas and writes
+the next window batch (a masked request: step, the blend-only launch, one fd_window_gather_f32).  That is DDIM with eta = 0;
+every other scheduler runs the generic route through `guide.noise_pred` with the eager UNet (a planned route for them is out of
+scope).
+
 fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 (and their two noise forms) are one kernel (csrc/step.hip) over one
 statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
 wherever they compute the same thing.
@@ -63,7 +70,7 @@ from .. import hip, ops
 from ..encode.clip import preprocess
 from ..noise import PhiloxNoise
 from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler
-from .guide import GuideBase, SimpleGuide, check_guidance_rescale
+from .guide import GuideBase, SimpleGuide, WindowedGuide, check_guidance_rescale
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
 VAE_SCALE = 0.18215
@@ -403,6 +410,13 @@ class FlexPipeline():
                 and hasattr(self.unet, 'forward_nhwc'))
         simple = type(guide).noise_pred is SimpleGuide.noise_pred
         device_guide = simple or comp
+        # WindowedGuide: a canvas of any size on the UNet's own window size.  DDIM (eta = 0): the window batch is the loop's
+        # persistent buffer, the canvas an ordinary tensor, a step the UNet replay + one fd_window_step_f32; every other
+        # scheduler: the generic branch through guide.noise_pred
+        win = type(guide).noise_pred is WindowedGuide.noise_pred and hasattr(self.unet, 'forward_nhwc')
+        if win and rescale:
+            raise ValueError('WindowedGuide does not support guidance_rescale')
+        win_fused = win and isinstance(self.scheduler, DDIMScheduler) and not eta
         rescale = rescale if simple else 0.0     # any other guide applies (or ignores) its own attribute in its noise_pred
         # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
         step_noise = self.step_noise
@@ -431,7 +445,7 @@ class FlexPipeline():
         is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
         known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
         self._temb_tab = None
-        if (fused or fused_ms or planned) and hasattr(self.unet, 'time_bias_table'):
+        if (fused or fused_ms or planned or win_fused) and hasattr(self.unet, 'time_bias_table'):
             # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
             # instead of three GEMMs per step
             ts = [float(t) for t in self.scheduler.timesteps[t_start:]]
@@ -441,8 +455,17 @@ class FlexPipeline():
             self._temb_tab = (keys, self.unet.time_bias_table(list(keys)))
         # loop-invariant: the CFG switch and the UNet's batch replication of a device guide, DDIM's prediction type
         cfg = guide.classifier_free_guidance if device_guide else None
-        rep = guide.rep if comp else 2 if cfg else 1
-        vpred = fused and self.scheduler.config['prediction_type'] == 'v_prediction'
+        rep = guide.rep if comp or win else 2 if cfg else 1
+        vpred = (fused or win_fused) and self.scheduler.config['prediction_type'] == 'v_prediction'
+        if win_fused:
+            # the window batch: the one persistent buffer (what the graph / plan reads); the canvas does not evict it
+            grid = guide.bind(H, W)
+            wshape = (B * grid.count, C, grid.h, grid.w)
+            wins = self._lat_bufs.get(wshape)
+            if wins is None:
+                wins = torch.empty(wshape, dtype=torch.float32, device=latents.device)
+                self._lat_bufs = {wshape: wins}
+            guide.gather(latents, wins)
 
         # a guide with a context schedule (ScheduledGuide, CompositeGuide(style_linear=)): told the GLOBAL step index at the top of
         # every iteration, on every route; guides without `at_step` run as before
@@ -508,6 +531,22 @@ class FlexPipeline():
                                                   (step_noise, t_start + i))
                     else:
                         self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
+                elif win_fused:
+                    if debug:
+                        temb = self._temb_row(int(t)).expand(wins.shape[0] * rep, -1).contiguous() if self._temb_tab else None
+                        eps = self.unet.forward_nhwc(wins, int(t), guide.stacked_embeds(), rep=rep, temb=temb)
+                        latents = latents.clone()
+                    else:
+                        eps = self._unet_eps(wins, int(t), guide.stacked_embeds(), rep)
+                    coef = self.scheduler.step_coefficients(int(t), 0.0)[:4]
+                    if known is None:
+                        # CFG per window, the average, the DDIM update of the canvas and the next window batch in one launch
+                        guide.step(latents, wins, eps, coef, vpred)
+                    else:
+                        # the blend changes the canvas: step, blend, then the next window batch from the blended canvas
+                        guide.step(latents, None, eps, coef, vpred)
+                        blend_known(latents, i)
+                        guide.gather(latents, wins)
                 else:
                     t_index, model_input = t, latents
                     if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling

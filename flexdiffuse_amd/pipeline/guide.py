@@ -10,7 +10,7 @@ from typing import List, Optional, Sequence, Union
 
 import torch
 
-from .. import ops
+from .. import ops, windows
 from ..ctx_schedule import ContextSchedule, check_keyframes, step_weights
 
 
@@ -86,6 +86,96 @@ class PromptGuide(SimpleGuide):
                  guidance_rescale: float = 0.0):
         SimpleGuide.__init__(self, encoder, unet, guidance, steps, encoder.prompt(prompt), guidance_rescale=guidance_rescale)
         self.prompt = prompt
+
+
+class WindowedGuide(SimpleGuide):
+    '''SimpleGuide over a canvas larger than the model's own size (beyond the reference; MultiDiffusion, Bar-Tal et al. 2023):
+    the canvas latents are covered by overlapping windows (`windows.window_grid`), every step runs the UNet on all windows of
+    all samples as one batch, the guided predictions are averaged where windows overlap (`blend`: 'uniform', or 'tent'
+    weights that fall off towards a window's edge) and ONE scheduler step is taken on the canvas.  `window` and `stride` are
+    in image pixels, (height, width) or one int for both, divided by 8 as FlexPipeline divides `init_size`; the canvas is
+    whatever latents the guide is handed.  A canvas equal to the window is SimpleGuide, bit for bit.
+
+    `noise_pred` is the generic protocol (gather, eager UNet, combine-only fd_window_step_f32), so every scheduler and any
+    caller written against GuideBase works.  Under DDIM with eta = 0 FlexPipeline runs its device loop instead: the window
+    batch is the buffer its graph / launch plan reads, and a step is the UNet replay plus one fd_window_step_f32 (CFG,
+    average, DDIM update of the canvas, the next window batch).  A planned (graph) route for the other schedulers is out of
+    scope: they take the generic route with the eager UNet.  `guidance_rescale` is not supported (its standard deviations
+    would have to span the canvas).'''
+
+    def __init__(self, encoder, unet, guidance: float, steps: int, clip_embeds: torch.Tensor, *, window=(512, 512),
+                 stride=(256, 256), blend: str = 'uniform', guidance_rescale: float = 0.0):
+        if guidance_rescale:
+            raise ValueError('WindowedGuide does not support guidance_rescale: the per-sample standard deviations would have '
+                             'to span the canvas')
+        SimpleGuide.__init__(self, encoder, unet, guidance, steps, clip_embeds)
+        self.window = tuple(v // 8 for v in windows.pair(window))        # latent cells, (h, w)
+        self.stride = tuple(v // 8 for v in windows.pair(stride))
+        self.blend = blend
+        self.blend_code = windows.check_blend(blend)
+        # what the UNet asks of a latent's extents: one halving per level below the first
+        chans = (getattr(unet, 'config', None) or {}).get('block_out_channels')
+        self._multiple = 2 ** (len(chans) - 1) if chans else 1
+        # the geometry errors that do not depend on the canvas surface here, not at the first step
+        windows.window_grid(*self.window, *self.window, *self.stride, multiple=self._multiple)
+        self.on_device = True
+        self._grids = {}
+        self._count = 1                          # windows per sample of the canvas last bound
+        self._wstack = None
+
+    @property
+    def rep(self) -> int:
+        return 2 if self.classifier_free_guidance else 1
+
+    def grid(self, H: int, W: int) -> 'windows.WindowGrid':
+        '''The window grid over an (H, W) canvas of latent cells (ValueError: windows.window_grid).'''
+        g = self._grids.get((H, W))
+        if g is None:
+            g = self._grids[(H, W)] = windows.window_grid(H, W, *self.window, *self.stride, multiple=self._multiple)
+        return g
+
+    def stacked_embeds(self, count: Optional[int] = None) -> torch.Tensor:
+        '''[uncond] * (B Wn), then each sample's embedding repeated Wn times: built once per window count (default: the
+        count of the last canvas seen).'''
+        count = self._count if count is None else count
+        if self._wstack is None or self._wstack[0] != count or self._wstack[1] is not self.embeds:
+            ctx = windows.window_context(self.uncond_embeds, self.embeds, count, self.classifier_free_guidance)
+            self._wstack = (count, self.embeds, ctx)
+        return self._wstack[2]
+
+    def bind(self, H: int, W: int) -> 'windows.WindowGrid':
+        '''Fix the canvas of the running request: `stacked_embeds()` is then the context of its window batch.'''
+        g = self.grid(H, W)
+        self._count = g.count
+        return g
+
+    def gather(self, canvas: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        '''The window batch (B Wn, C, h, w) of a canvas (B, C, H, W): one launch.'''
+        B, C, H, W = canvas.shape
+        g = self.bind(H, W)
+        if out is None:
+            out = torch.empty((B * g.count, C, g.h, g.w), dtype=torch.float32, device=canvas.device)
+        ops.window_gather(canvas, out, B, C, g.args)
+        return out
+
+    def step(self, x: Optional[torch.Tensor], wins: Optional[torch.Tensor], eps: torch.Tensor, coef=(0.0, 1.0, 1.0, 0.0),
+             v_prediction: bool = False, eps_out: Optional[torch.Tensor] = None):
+        '''CFG + average of the UNet output `eps` over the window batch (NHWC fp32) into `eps_out` (NCHW fp32 canvas,
+        optional) and, given the canvas `x`, its DDIM update in place plus -- given `wins` -- the next window batch:
+        one launch.'''
+        B, C, H, W = (x if x is not None else eps_out).shape
+        ops.window_step(x, wins, eps, B, C, self.grid(H, W).args, self.blend_code, self.classifier_free_guidance,
+                        self.guidance, coef, v_prediction, do_step=x is not None, eps_out=eps_out)
+
+    def noise_pred(self, latents: torch.Tensor, step) -> torch.Tensor:
+        if self.guidance_rescale:
+            raise ValueError('WindowedGuide does not support guidance_rescale')
+        latents = latents.to(torch.float32).contiguous()
+        wins = self.gather(latents)
+        eps = self.unet.forward_nhwc(wins, step, self.stacked_embeds(), rep=self.rep)
+        out = torch.empty_like(latents)
+        self.step(None, None, eps, eps_out=out)
+        return out
 
 
 class ScheduledGuide(SimpleGuide):

@@ -28,7 +28,7 @@ from .encode.clip import CLIPEncoder
 from .guidance import Guide
 from .composition import CompositeGuide, EntitySchema, Schema
 from .noise import PhiloxNoise
-from .pipeline.guide import GuideBase, ScheduledGuide, SimpleGuide
+from .pipeline.guide import GuideBase, ScheduledGuide, SimpleGuide, WindowedGuide
 from .scheduler import DPMSolverMultistepSDEScheduler
 
 MAX_SEED = 2147483647          # the reference clamps seeds to int32 (utils.py:22)
@@ -178,12 +178,30 @@ class Runner():
         given.apply_defaults()
         return self._gen(dict(given.arguments), (end_prompt, end_guide, schedule))
 
-    def _gen(self, given: Dict[str, Any], travel=None):
+    def gen_wide(self, prompt='', *, size: Tuple[int, int] = (512, 1536), window=512, stride=256, blend: str = 'uniform',
+                 **gen_args):
+        '''`gen` on a canvas larger or wider than the model's size (beyond the reference; `WindowedGuide`, MultiDiffusion):
+        `size` is the image's (height, width), covered by overlapping `window`s at `stride` (image pixels; an int means both
+        axes) whose predictions are averaged ('uniform') or tent-weighted ('tent') where they overlap.  Every other
+        argument is `gen`'s, by keyword (`gen` itself keeps the reference's signature); `init_size` is `size`.'''
+        given = inspect.signature(Runner.gen).bind(self, prompt, **gen_args)
+        given.apply_defaults()
+        given = dict(given.arguments)
+        given['init_size'] = tuple(size)
+        return self._gen(given, wide=(window, stride, blend))
+
+    def _gen(self, given: Dict[str, Any], travel=None, wide=None):
         self._set_seed(given['seed'])
         params = {k: given[k] for k in _EMBEDS_KEYS}
         unet, scale, steps = self.pipe.unet, given['guidance_scale'], given['steps']
         embeds = self.guide.embeds(prompt=given['prompt'], guide=given['guide'], **params)
-        if travel is None:
+        if wide is not None:
+            window, stride, blend = wide
+            if self.guidance_rescale:
+                raise ValueError('gen_wide does not support Runner.guidance_rescale: its standard deviations would have to '
+                                 'span the canvas')
+            g = WindowedGuide(self.encoder, unet, scale, steps, embeds, window=window, stride=stride, blend=blend)
+        elif travel is None:
             g = SimpleGuide(self.encoder, unet, scale, steps, embeds, guidance_rescale=self.guidance_rescale)
         else:
             end_prompt, end_guide, schedule = travel

@@ -594,6 +594,31 @@ int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0
  * cached projections of its keyframes (UNet2DConditionModel.blend_context).  16-byte accesses when a, b and out are all 16-byte
  * aligned, a scalar kernel otherwise; out may alias neither input (FD_EINVAL, as are NULL pointers and n <= 0). */
 int fd_lerp_f16(const void* a, const void* b, void* out, int64_t n, float w, void* stream);
+/* Windowed (MultiDiffusion, Bar-Tal et al. 2023) sampling on the device loop (additive; FD_ABI_VERSION stays 12): a canvas
+ * latent (B, C, H, W) is covered by ny x nx overlapping windows (h, w) of the model's own size, the UNet runs on all of them
+ * as one batch, and the guided predictions are averaged where windows overlap before one step on the canvas.  The grid is
+ * plain ints: along an axis of extent S, window s, stride d (1 <= d <= s <= S) there are n = ceil((S - s) / d) + 1 <= 16
+ * windows at offsets o_i = min(i d, S - s) (the last snapped to the edge); ny, nx must be those counts.  Window (iy, ix) is
+ * w = iy nx + ix of Wn = ny nx; sample b, window w is row b Wn + w of the window batch.  Anything else is FD_EINVAL.
+ * fd_window_gather_f32: windows (B Wn, C, h, w) NCHW fp32 <- the canvas cells under each window. */
+int fd_window_gather_f32(const float* canvas, float* windows, int B, int C, int H, int W, int h, int w, int stride_y,
+                         int stride_x, int ny, int nx, void* stream);
+/* One launch per step after the UNet.  eps_nhwc: the UNet output, fp32, row ((r B Wn + b Wn + w) h w + p), r = 0
+ * unconditional / 1 conditional (r = 0 only without cfg), p = ly w + lx, row stride ld >= C.  Per canvas cell (b, y, x) and
+ * channel, every operation a separately rounded fp32 one:
+ *   acc = 0, wsum = 0 ;  for every window covering the cell, in ascending (iy, ix) order:
+ *     g_w = u_w + guidance (t_w - u_w) (cfg; otherwise the one row)
+ *     blend 0 (uniform): acc = acc + g_w ;  blend 1 (tent): wgt = min(ly + 1, h - ly) min(lx + 1, w - lx) (an exact integer),
+ *     acc = acc + wgt g_w, wsum = wsum + wgt
+ *   e = g_w where exactly one window covers the cell (an exact branch), else acc / count (uniform) | acc / wsum (tent)
+ *   eps_out (optional, NCHW fp32 [B][C][H][W]) <- e ;  do_step: x <- x' = the DDIM (eta = 0) update of fd_cfg_ddim_step_f32
+ *   (same coefficients, eps- or v-prediction) ;  windows_out (optional, needs do_step) <- x' in the cell of every covering
+ *   window -- the next step's UNet input; each window cell has one source, so there are no atomics.
+ * do_step == 0 is the combine-only form: eps_out is required and windows_out must be NULL.  On a one-window grid the uniform
+ * form gives the bits of fd_cfg_ddim_step_f32. */
+int fd_window_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, int B, int C, int ld, int H,
+                       int W, int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance,
+                       float c1, float c2, float c3, float c4, int v_prediction, int do_step, void* stream);
 /* Contiguous casts: fp32 -> fp16 rounds to nearest even (overflow to inf from 65520 on), fp16 -> fp32 is exact. */
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
