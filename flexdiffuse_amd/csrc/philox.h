@@ -19,6 +19,20 @@ struct FdNoiseAddr {
     int per;                    // elements per sample
 };
 
+// the noise address of a launch over `total` elements; the checks every noise entry point (step.hip, window.hip) shares
+static inline int fd_noise_addr(const char* who, uint64_t seed, int64_t sample_offset, int per, int draw,
+                                int noise_stream, unsigned long long total, FdNoiseAddr* out) {
+    FD_CHECK_ARG(per > 0 && total % (unsigned long long)per == 0, FD_EINVAL,
+                 "%s: sizes: per must be positive and divide the element count", who);
+    FD_CHECK_ARG(sample_offset >= 0 && draw >= 0 && noise_stream >= 0, FD_EINVAL,
+                 "%s: sizes: negative sample_offset, draw or stream", who);
+    FD_CHECK_ARG((unsigned long long)sample_offset + total / (unsigned long long)per <= (1ull << 32), FD_EINVAL,
+                 "%s: sizes: sample index past 2^32", who);
+    *out = {(unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), (unsigned)sample_offset, (unsigned)draw,
+            (unsigned)noise_stream, per};
+    return FD_OK;
+}
+
 __device__ __forceinline__ void fd_philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
                                                  unsigned k1, unsigned (&w)[4]) {
 #pragma unroll

@@ -21,8 +21,6 @@
 #include "latent_step.h"
 #include "philox.h"
 
-enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2 };
-
 // Optional pointers are NULL when unused (uniform across the grid).  co: DDIM c1 c2 c3 c4 | multistep p q a w0 w1.
 struct FdStepArgs {
     float* x;
@@ -66,11 +64,9 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
     } else if constexpr (UPDATE == FD_STEP_MULTISTEP) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
-            const float d0 = __fadd_rn(__fmul_rn(a.co[0], xv[j]), __fmul_rn(a.co[1], ev[j]));
-            float xn = __fadd_rn(__fmul_rn(a.co[2], xv[j]), __fmul_rn(a.co[3], d0));
-            if (a.m1) xn = __fadd_rn(xn, __fmul_rn(a.co[4], hv[j]));
+            float d0;
+            xv[j] = fd_multistep_update(xv[j], ev[j], a.m1 ? hv[j] : 0.f, a.m1 != nullptr, a.co, d0);
             ev[j] = d0;
-            xv[j] = xn;
         }
         fd_stv<V>(a.m0_out + e, ev);
     }
@@ -228,20 +224,7 @@ extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float*
 }
 
 // ---- the stochastic forms ------------------------------------------------------------------------------------------
-// the noise address of a launch over `total` elements; the checks every noise entry point shares
-static int fd_noise_addr(const char* who, uint64_t seed, int64_t sample_offset, int per, int draw,
-                         int noise_stream, unsigned long long total, FdNoiseAddr* out) {
-    FD_CHECK_ARG(per > 0 && total % (unsigned long long)per == 0, FD_EINVAL,
-                 "%s: sizes: per must be positive and divide the element count", who);
-    FD_CHECK_ARG(sample_offset >= 0 && draw >= 0 && noise_stream >= 0, FD_EINVAL,
-                 "%s: sizes: negative sample_offset, draw or stream", who);
-    FD_CHECK_ARG((unsigned long long)sample_offset + total / (unsigned long long)per <= (1ull << 32), FD_EINVAL,
-                 "%s: sizes: sample index past 2^32", who);
-    *out = {(unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), (unsigned)sample_offset, (unsigned)draw,
-            (unsigned)noise_stream, per};
-    return FD_OK;
-}
-
+// (fd_noise_addr, philox.h: the noise address of a launch and the checks every noise entry point shares)
 extern "C" int fd_cfg_ddim_noise_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise,
                                           const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
                                           float c1, float c2, float c3, float c4, int v_prediction, float k1, float k2,

@@ -4,13 +4,20 @@
 //   fd_window_gather_f32   canvas (B, C, H, W) -> window batch (B Wn, C, h, w), before the first step and after a blend
 //   fd_window_step_f32     one launch per step after the UNet: CFG per window, the average over the covering windows
 //                          (-> eps_out), the DDIM (eta = 0) update of the canvas and the next step's window batch
+//   fd_window_ddim_step_f32       that step with, optionally, the step noise sigma z (DDIM eta > 0) and the known-region
+//                                 blend of masked img2img, in the same launch
+//   fd_window_multistep_step_f32  DPM-Solver++ (2M) and its SDE form on the canvas: the data prediction -> m0_out, the
+//                                 multistep update, + sn z, the blend, the next window batch
+// All three are fronts of ONE kernel, k_window_step<V, UPDATE, NOISE>, the sibling of k_latent_step (step.hip) with the
+// same three axes; the noise is the stream of philox.h at the CANVAS element, so it does not depend on the window grid.
 // The grid travels as plain ints (H, W, h, w, stride_y, stride_x, ny, nx): along an axis of extent S with windows of
 // extent s and stride d there are n = ceil((S - s) / d) + 1 windows at offsets o_i = min(i d, S - s) -- the last one
 // snapped to the edge.  Window (iy, ix) is w = iy nx + ix; sample b, window w is row b Wn + w of the UNet batch.
 // Every operation is one of latent_step.h or a separately rounded fp32 intrinsic, in the order written in
 // include/flexdiffuse_hip.h, so the step is bit-equal to an fp32 torch restatement and, on a one-window grid, to
-// fd_cfg_ddim_step_f32.
+// fd_cfg_ddim_step_f32 (the other two fronts: to fd_cfg_ddim_noise_step_f32 / fd_cfg_multistep_[noise_]step_f32).
 #include "latent_step.h"
+#include "philox.h"
 
 enum { FD_WINDOW_MAX = 16, FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
 
@@ -43,21 +50,38 @@ __global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__
     }
 }
 
+// Optional pointers are NULL when unused (uniform across the grid).  co: DDIM c1 c2 c3 c4 | multistep p q a w0 w1.
+struct FdWindowStepArgs {
+    float *x, *wout;
+    const float* eps;
+    float *eps_out, *m0_out;
+    const float *m1, *z0, *nz, *mask;          // m1, m0_out, z0, nz: canvas-shaped; mask: [H][W]
+    int B, C, ld, tent, cfg, vpred;
+    FdWindowGrid g;
+    float gscale, co[5], k1, k2;
+    float sn;                                   // noise coefficient (NOISE kernels)
+    FdNoiseAddr nz_addr;                        // per = C H W: the noise is addressed by the CANVAS element
+};
+
 // One thread owns one canvas cell (b, y, x) and all C channels; consecutive threads run along x, so every NCHW plane is
 // written in whole rows.  V = 4: float4 loads along the channels of the eps rows (C % 4 == 0, ld % 4 == 0, 16-byte base).
-template <int V>
-__global__ __launch_bounds__(256) void k_window_step(float* __restrict__ x, float* __restrict__ wout,
-                                                     const float* __restrict__ eps, float* __restrict__ eps_out, int B,
-                                                     int C, int ld, const FdWindowGrid g, int tent, int cfg, float gscale,
-                                                     float c1, float c2, float c3, float c4, int vpred, int do_step) {
+// UPDATE, NOISE: the axes of k_latent_step (step.hip), in its order -- e -> eps_out ; the update ; + sn z ; d0 -> m0_out ; the
+// blend (mask) ; -> x and the cell of every covering window.  A thread's channels are H W apart, so the noise is looked up
+// per element: the value is a function of the canvas element's address alone, never of the window grid.
+template <int V, int UPDATE, bool NOISE>
+__global__ __launch_bounds__(256) void k_window_step(const FdWindowStepArgs a) {
+    const FdWindowGrid& g = a.g;
+    const float* __restrict__ eps = a.eps;
+    const int C = a.C, ld = a.ld;
     const int Wn = g.ny * g.nx, hw = g.h * g.w;
     const size_t HW = (size_t)g.H * g.W;
-    const size_t total = (size_t)B * HW;
-    const size_t half = (size_t)B * Wn * hw * ld;        // the conditional rows follow the unconditional ones
+    const size_t total = (size_t)a.B * HW;
+    const size_t half = (size_t)a.B * Wn * hw * ld;      // the conditional rows follow the unconditional ones
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const int px = e % g.W;
         const int py = (e / g.W) % g.H;
         const int b = e / HW;
+        const float m = UPDATE != FD_STEP_NONE && a.mask ? a.mask[(size_t)py * g.W + px] : 1.f;
         for (int c0 = 0; c0 < C; c0 += V) {
             float acc[V], last[V], u[V], t[V];
 #pragma unroll
@@ -71,15 +95,15 @@ __global__ __launch_bounds__(256) void k_window_step(float* __restrict__ x, floa
                     const int lx = px - fd_window_offset(ix, g.sx, g.W, g.w);
                     if (lx < 0 || lx >= g.w) continue;
                     const size_t row = (((size_t)b * Wn + iy * g.nx + ix) * hw + (size_t)ly * g.w + lx) * ld + c0;
-                    if (cfg) {
+                    if (a.cfg) {
                         fd_ldv<V>(eps + row, u);
                         fd_ldv<V>(eps + half + row, t);
 #pragma unroll
-                        for (int j = 0; j < V; ++j) last[j] = fd_cfg_mix(u[j], t[j], gscale);
+                        for (int j = 0; j < V; ++j) last[j] = fd_cfg_mix(u[j], t[j], a.gscale);
                     } else {
                         fd_ldv<V>(eps + row, last);
                     }
-                    if (tent) {
+                    if (a.tent) {
                         const float wgt = (float)(min(ly + 1, g.h - ly) * min(lx + 1, g.w - lx));
 #pragma unroll
                         for (int j = 0; j < V; ++j) acc[j] = __fadd_rn(acc[j], __fmul_rn(wgt, last[j]));
@@ -92,19 +116,30 @@ __global__ __launch_bounds__(256) void k_window_step(float* __restrict__ x, floa
                 }
             }
             // the exact branch is part of the contract: (w g) / w is not g in fp32
-            const float den = tent ? wsum : (float)count;
+            const float den = a.tent ? wsum : (float)count;
 #pragma unroll
             for (int j = 0; j < V; ++j) {
                 float v = count == 1 ? last[j] : __fdiv_rn(acc[j], den);
                 const size_t o = ((size_t)b * C + c0 + j) * HW + (size_t)py * g.W + px;     // NCHW canvas
-                if (eps_out) eps_out[o] = v;
-                if (do_step) {
-                    v = fd_ddim_update(x[o], v, c1, c2, c3, c4, vpred);
-                    x[o] = v;
+                if (a.eps_out) a.eps_out[o] = v;
+                if constexpr (UPDATE != FD_STEP_NONE) {
+                    float d0 = 0.f;
+                    if constexpr (UPDATE == FD_STEP_DDIM)
+                        v = fd_ddim_update(a.x[o], v, a.co[0], a.co[1], a.co[2], a.co[3], a.vpred);
+                    else
+                        v = fd_multistep_update(a.x[o], v, a.m1 ? a.m1[o] : 0.f, a.m1 != nullptr, a.co, d0);
+                    if constexpr (NOISE) {
+                        float z[1];
+                        fd_noise_normals<1>(a.nz_addr, o, z);
+                        v = __fadd_rn(v, __fmul_rn(a.sn, z[0]));
+                    }
+                    if constexpr (UPDATE == FD_STEP_MULTISTEP) a.m0_out[o] = d0;
+                    if (a.mask) v = fd_known_blend(v, a.z0[o], a.nz[o], m, a.k1, a.k2);
+                    a.x[o] = v;
                 }
                 last[j] = v;
             }
-            if (!wout) continue;
+            if (UPDATE == FD_STEP_NONE || !a.wout) continue;
             // the next UNet input: this cell of every covering window has exactly this one source
             for (int iy = 0; iy < g.ny; ++iy) {
                 const int ly = py - fd_window_offset(iy, g.sy, g.H, g.h);
@@ -112,7 +147,7 @@ __global__ __launch_bounds__(256) void k_window_step(float* __restrict__ x, floa
                 for (int ix = 0; ix < g.nx; ++ix) {
                     const int lx = px - fd_window_offset(ix, g.sx, g.W, g.w);
                     if (lx < 0 || lx >= g.w) continue;
-                    float* dst = wout + (((size_t)b * Wn + iy * g.nx + ix) * C + c0) * hw + (size_t)ly * g.w + lx;
+                    float* dst = a.wout + (((size_t)b * Wn + iy * g.nx + ix) * C + c0) * hw + (size_t)ly * g.w + lx;
 #pragma unroll
                     for (int j = 0; j < V; ++j) dst[(size_t)j * hw] = last[j];
                 }
@@ -153,6 +188,22 @@ extern "C" int fd_window_gather_f32(const float* canvas, float* windows, int B, 
     return FD_OK;
 }
 
+// V = 4 when the eps rows can be read as float4 along the channels, else V = 1; grid; launch.  sn == 0 launches the kernels
+// without the noise stage.
+static int fd_window_step_launch(int update, const FdWindowStepArgs& a, void* stream) {
+    const int noise = update != FD_STEP_NONE && a.sn != 0.f;
+    const int vec = a.C % 4 == 0 && a.ld % 4 == 0 && (uintptr_t)a.eps % 16 == 0;
+    static void (*const kernels[2][2][3])(const FdWindowStepArgs) = {
+        {{k_window_step<1, FD_STEP_NONE, false>, k_window_step<1, FD_STEP_DDIM, false>, k_window_step<1, FD_STEP_MULTISTEP, false>},
+         {k_window_step<4, FD_STEP_NONE, false>, k_window_step<4, FD_STEP_DDIM, false>, k_window_step<4, FD_STEP_MULTISTEP, false>}},
+        {{nullptr, k_window_step<1, FD_STEP_DDIM, true>, k_window_step<1, FD_STEP_MULTISTEP, true>},
+         {nullptr, k_window_step<4, FD_STEP_DDIM, true>, k_window_step<4, FD_STEP_MULTISTEP, true>}}};
+    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(fd_grid1d((size_t)a.B * a.g.H * a.g.W, 2048)), dim3(256), 0,
+                       (hipStream_t)stream, a);
+    FD_CHECK_LAUNCH("k_window_step");
+    return FD_OK;
+}
+
 extern "C" int fd_window_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, int B, int C, int ld,
                                   int H, int W, int h, int w, int stride_y, int stride_x, int ny, int nx, int blend,
                                   int cfg, float guidance, float c1, float c2, float c3, float c4, int v_prediction,
@@ -173,14 +224,71 @@ extern "C" int fd_window_step_f32(float* x, float* windows_out, const float* eps
     FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "fd_window_step_f32: eps_out aliases the canvas");
     FD_CHECK_ARG(!windows_out || (windows_out != x && windows_out != eps_out), FD_EINVAL,
                  "fd_window_step_f32: windows_out aliases the canvas or eps_out");
-    const int blocks = fd_grid1d((size_t)B * H * W, 2048);
-    const bool vec = C % 4 == 0 && ld % 4 == 0 && (uintptr_t)eps_nhwc % 16 == 0;
-    if (vec)
-        hipLaunchKernelGGL(k_window_step<4>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, windows_out, eps_nhwc,
-                           eps_out, B, C, ld, g, blend, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
-    else
-        hipLaunchKernelGGL(k_window_step<1>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x, windows_out, eps_nhwc,
-                           eps_out, B, C, ld, g, blend, cfg ? 1 : 0, guidance, c1, c2, c3, c4, v_prediction, do_step);
-    FD_CHECK_LAUNCH("k_window_step");
+    const FdWindowStepArgs a = {x, windows_out, eps_nhwc, eps_out, nullptr, nullptr, nullptr, nullptr, nullptr, B, C, ld, blend,
+                                cfg ? 1 : 0, v_prediction, g, guidance, {c1, c2, c3, c4, 0.f}, 1.f, 0.f, 0.f, {}};
+    return fd_window_step_launch(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
+}
+
+// the checks the DDIM and multistep fronts share after their own null checks: grid, sizes, blend, the known-region blend
+// and every alias a launch could trip over (windows_out is written while the canvas-shaped buffers are still being read)
+static int fd_window_front_args(const char* who, const FdWindowStepArgs& a) {
+    const int rc = fd_window_grid_args(who, a.B, a.C, a.g);
+    if (rc != FD_OK) return rc;
+    FD_CHECK_ARG(a.ld >= a.C, FD_EINVAL, "%s: sizes: ld %d < C %d", who, a.ld, a.C);
+    FD_CHECK_ARG(a.tent == FD_BLEND_UNIFORM || a.tent == FD_BLEND_TENT, FD_EINVAL,
+                 "%s: blend %d is neither uniform (0) nor tent (1)", who, a.tent);
+    FD_CHECK_ARG(!a.mask || (a.z0 && a.nz), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
+    FD_CHECK_ARG(!a.mask || (a.x != a.z0 && a.x != a.nz), FD_EINVAL, "%s: z0 / noise alias the canvas", who);
+    FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x, FD_EINVAL, "%s: eps_out aliases the canvas", who);
+    const void* others[] = {a.x, a.eps, a.eps_out, a.m0_out, a.m1, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr, a.mask};
+    for (const void* o : others)
+        FD_CHECK_ARG(!a.wout || a.wout != o, FD_EINVAL, "%s: windows_out aliases another buffer of the call", who);
     return FD_OK;
+}
+
+// the noise address of a front: per = C H W, the launch's first sample at sample_offset, stream 0
+static int fd_window_noise(const char* who, FdWindowStepArgs& a, uint64_t seed, int64_t sample_offset, int draw) {
+    const unsigned long long per = (unsigned long long)a.C * a.g.H * a.g.W;
+    FD_CHECK_ARG(per <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * H * W past 2^31", who);
+    return fd_noise_addr(who, seed, sample_offset, (int)per, draw, 0, per * a.B, &a.nz_addr);
+}
+
+extern "C" int fd_window_ddim_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, const float* z0,
+                                       const float* noise, const float* mask, int B, int C, int ld, int H, int W, int h,
+                                       int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg,
+                                       float guidance, float c1, float c2, float c3, float c4, int v_prediction, float k1,
+                                       float k2, float sigma, uint64_t seed, int64_t sample_offset, int draw, void* stream) {
+    FD_PLAN(fd_window_ddim_step_f32(x, windows_out, eps_nhwc, eps_out, z0, noise, mask, B, C, ld, H, W, h, w, stride_y,
+                                    stride_x, ny, nx, blend, cfg, guidance, c1, c2, c3, c4, v_prediction, k1, k2, sigma, seed,
+                                    sample_offset, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_window_ddim_step_f32: x or eps_nhwc is null");
+    FdWindowStepArgs a = {x, windows_out, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, ld, blend,
+                          cfg ? 1 : 0, v_prediction, {H, W, h, w, stride_y, stride_x, ny, nx}, guidance,
+                          {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
+    int rc = fd_window_front_args("fd_window_ddim_step_f32", a);
+    if (rc != FD_OK) return rc;
+    if (sigma != 0.f && (rc = fd_window_noise("fd_window_ddim_step_f32", a, seed, sample_offset, draw)) != FD_OK) return rc;
+    return fd_window_step_launch(FD_STEP_DDIM, a, stream);
+}
+
+extern "C" int fd_window_multistep_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* m0_out,
+                                            const float* m1, const float* z0, const float* noise, const float* mask, int B,
+                                            int C, int ld, int H, int W, int h, int w, int stride_y, int stride_x, int ny,
+                                            int nx, int blend, int cfg, float guidance, float p, float q, float a, float w0,
+                                            float w1, float k1, float k2, float sn, uint64_t seed, int64_t sample_offset,
+                                            int draw, void* stream) {
+    FD_PLAN(fd_window_multistep_step_f32(x, windows_out, eps_nhwc, m0_out, m1, z0, noise, mask, B, C, ld, H, W, h, w, stride_y,
+                                         stride_x, ny, nx, blend, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed,
+                                         sample_offset, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "fd_window_multistep_step_f32: x, eps_nhwc or m0_out is null");
+    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_window_multistep_step_f32: m0_out aliases the canvas or m1");
+    FdWindowStepArgs s = {x, windows_out, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, ld, blend,
+                          cfg ? 1 : 0, 0, {H, W, h, w, stride_y, stride_x, ny, nx}, guidance,
+                          {p, q, a, w0, w1}, k1, k2, sn, {}};
+    int rc = fd_window_front_args("fd_window_multistep_step_f32", s);
+    if (rc != FD_OK) return rc;
+    if (sn != 0.f && (rc = fd_window_noise("fd_window_multistep_step_f32", s, seed, sample_offset, draw)) != FD_OK) return rc;
+    return fd_window_step_launch(FD_STEP_MULTISTEP, s, stream);
 }

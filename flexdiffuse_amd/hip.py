@@ -107,6 +107,9 @@ _SIGNATURES = {
     'fd_xattn_fold_rows_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'fd_window_gather_f32': (c_int, [P, P] + [c_int] * 10 + [P]),
     'fd_window_step_f32': (c_int, [P, P, P, P] + [c_int] * 13 + [c_float] * 5 + [c_int, c_int, P]),
+    'fd_window_ddim_step_f32': (c_int, [P] * 7 + [c_int] * 13 + [c_float] * 5 + [c_int] + [c_float] * 3
+                                + [c_uint64, c_int64, c_int, P]),
+    'fd_window_multistep_step_f32': (c_int, [P] * 8 + [c_int] * 13 + [c_float] * 9 + [c_uint64, c_int64, c_int, P]),
     'fd_cast_f32_to_f16': (c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

@@ -1252,6 +1252,50 @@ def window_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], 
              float(coef[3]), int(v_prediction), int(do_step), hip.stream())
 
 
+def _window_blend_noise(B: int, C: int, grid, x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor,
+                        cfg: bool, mask, sn: float, noise):
+    '''The checks the two windowed step fronts share; returns (z0, nz, mask, k1, k2, seed, sample_offset).'''
+    H, W, h, w, _, _, ny, nx = grid
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(B * C * H * W, x, z0, nz)
+    _check_f32(H * W, mk)
+    _check_f32(B * ny * nx * C * h * w, windows_out)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * ny * nx * h * w, C)
+    assert not sn or noise is not None, 'a noise coefficient without a PhiloxNoise'
+    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+    return z0, nz, mk, float(k1), float(k2), seed, offset
+
+
+def window_ddim_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, grid,
+                     blend: int, cfg: bool, guidance: float, coef, v_prediction: bool = False, mask=None, sigma: float = 0.0,
+                     noise=None, draw: int = 0, eps_out: Optional[torch.Tensor] = None):
+    '''Windowed DDIM step (fd_window_ddim_step_f32): `window_step` with, in the same launch, x' += sigma z (sigma != 0; z the
+    stream of `noise`, a `PhiloxNoise`, at `draw`, addressed by the canvas element: C H W elements per sample) and, with
+    mask = (z0, noise, mask [H W], k1, k2), the known-region blend of `cfg_ddim_masked_step` on the canvas; windows_out
+    receives the blended canvas.  Neither: the bits of `window_step`.'''
+    z0, nz, mk, k1, k2, seed, offset = _window_blend_noise(B, C, grid, x, windows_out, eps_nhwc, cfg, mask, sigma, noise)
+    _check_f32(x.numel(), eps_out)
+    hip.call('fd_window_ddim_step_f32', x.data_ptr(), _p(windows_out), eps_nhwc.data_ptr(), _p(eps_out), _p(z0), _p(nz),
+             _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg), float(guidance), float(coef[0]),
+             float(coef[1]), float(coef[2]), float(coef[3]), int(v_prediction), k1, k2, float(sigma), seed, offset, int(draw),
+             hip.stream())
+
+
+def window_multistep_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, m0_out: torch.Tensor,
+                          m1: Optional[torch.Tensor], B: int, C: int, grid, blend: int, cfg: bool, guidance: float, coef,
+                          mask=None, sn: float = 0.0, noise=None, draw: int = 0):
+    '''Windowed DPM-Solver++ step (fd_window_multistep_step_f32), in place on the canvas x: e = the windows' guided average of
+    `window_step`; m0 = p x + q e -> m0_out; x' = a x + w0 m0 (+ w1 m1 when m1 is given), coef = (p, q, a, w0, w1); x' += sn z
+    (sn != 0: the SDE form, z as in `window_ddim_step`); the blend of `mask`; windows_out (optional) <- the next window
+    batch.  m0_out and m1 are canvas-shaped.'''
+    z0, nz, mk, k1, k2, seed, offset = _window_blend_noise(B, C, grid, x, windows_out, eps_nhwc, cfg, mask, sn, noise)
+    _check_f32(x.numel(), m0_out, m1)
+    hip.call('fd_window_multistep_step_f32', x.data_ptr(), _p(windows_out), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1),
+             _p(z0), _p(nz), _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg), float(guidance),
+             float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), k1, k2, float(sn), seed, offset,
+             int(draw), hip.stream())
+
+
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
           exp_half_x: bool = False) -> torch.Tensor:
     assert x.dtype == torch.float32 and (y is None or (y.dtype == torch.float32 and y.numel() == x.numel())), \

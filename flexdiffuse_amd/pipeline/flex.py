@@ -42,10 +42,13 @@ routes -- the same bits on every route.  With 0 every route makes the calls it m
 
 Windowed sampling (`WindowedGuide`, beyond the reference; MultiDiffusion, Bar-Tal et al. 2023; windows.py): a canvas larger than
 the model's size is covered by overlapping windows, the UNet runs on all of them as one batch -- the loop's persistent buffer,
-through the graph / plan -- and one fd_window_step_f32 per step combines, averages, takes the DDIM step on the canvas and writes
-the next window batch (a masked request: step, the blend-only launch, one fd_window_gather_f32).  That is DDIM with eta = 0;
-every other scheduler runs the generic route through `guide.noise_pred` with the eager UNet (a planned route for them is out of
-scope).
+through the graph / plan -- and ONE launch per step combines, averages, takes the step on the canvas and writes the next window
+batch: fd_window_step_f32 (DDIM, eta = 0), fd_window_ddim_step_f32 (a masked request's known-region blend and, with
+`pipe.step_noise`, DDIM's eta > 0 term in that launch), fd_window_multistep_step_f32 (DPM-Solver++ and its SDE form, masked or
+not).  The step noise is addressed by the canvas element (draw = t_start + i), never by the window grid.  PNDM, K-LMS and DDIM
+with eta > 0 on generator noise take a planned route: one fd_window_gather_f32 into the persistent window batch, the graph /
+plan replay, the combine-only form, `scheduler.step`, the blend-only launch of a masked request -- the bits of the loop over
+`guide.noise_pred`, which remains the route of `debug=True` and of a pipeline with neither graph nor plan.
 
 fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 (and their two noise forms) are one kernel (csrc/step.hip) over one
 statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
@@ -410,13 +413,14 @@ class FlexPipeline():
                 and hasattr(self.unet, 'forward_nhwc'))
         simple = type(guide).noise_pred is SimpleGuide.noise_pred
         device_guide = simple or comp
-        # WindowedGuide: a canvas of any size on the UNet's own window size.  DDIM (eta = 0): the window batch is the loop's
-        # persistent buffer, the canvas an ordinary tensor, a step the UNet replay + one fd_window_step_f32; every other
-        # scheduler: the generic branch through guide.noise_pred
+        # WindowedGuide: a canvas of any size on the UNet's own window size.  The window batch is the loop's persistent buffer,
+        # the canvas an ordinary tensor.  DDIM (eta = 0, or eta > 0 on the counter-based stream) and DPM-Solver++ (ODE and
+        # SDE): a step is the UNet replay + ONE launch (win_fused, below); every other scheduler: the planned route (gather,
+        # replay, combine-only, scheduler.step), or with debug / without graph and plan the generic branch through
+        # guide.noise_pred
         win = type(guide).noise_pred is WindowedGuide.noise_pred and hasattr(self.unet, 'forward_nhwc')
         if win and rescale:
             raise ValueError('WindowedGuide does not support guidance_rescale')
-        win_fused = win and isinstance(self.scheduler, DDIMScheduler) and not eta
         rescale = rescale if simple else 0.0     # any other guide applies (or ignores) its own attribute in its noise_pred
         # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
         step_noise = self.step_noise
@@ -425,6 +429,10 @@ class FlexPipeline():
             step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
         # eta > 0 stays fused for SimpleGuide when the noise comes from the counter-based stream (fd_cfg_ddim_noise_step_f32)
         noisy = bool(eta) and step_noise is not None and simple
+        # the windowed device loop: DDIM (its eta > 0 term from the stream, win_noisy) or the multistep solver (win_ms)
+        win_ms = win and isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        win_noisy = win and bool(eta) and step_noise is not None and isinstance(self.scheduler, DDIMScheduler)
+        win_fused = win_ms or win_noisy or (win and isinstance(self.scheduler, DDIMScheduler) and not eta)
         fused = (device_guide
                  and isinstance(self.scheduler, DDIMScheduler) and (not eta or noisy)
                  and hasattr(self.unet, 'forward_nhwc'))
@@ -439,13 +447,15 @@ class FlexPipeline():
         # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
         planned = (not fused and not fused_ms and device_guide and hasattr(self.unet, 'forward_nhwc')
                    and (self.use_graph or self.use_plan) and not debug)
+        # WindowedGuide with any scheduler the windowed loop does not step itself: the same route over the window batch
+        win_planned = win and not win_fused and (self.use_graph or self.use_plan) and not debug
         if (fused or fused_ms) and (self.use_graph or self.use_plan) and not debug:
             # persistent latent buffer: the captured UNet graph / recorded plan reads this address
             latents = self.loop_latents(latents)
         is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
         known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
         self._temb_tab = None
-        if (fused or fused_ms or planned or win_fused) and hasattr(self.unet, 'time_bias_table'):
+        if (fused or fused_ms or planned or win_fused or win_planned) and hasattr(self.unet, 'time_bias_table'):
             # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
             # instead of three GEMMs per step
             ts = [float(t) for t in self.scheduler.timesteps[t_start:]]
@@ -457,7 +467,7 @@ class FlexPipeline():
         cfg = guide.classifier_free_guidance if device_guide else None
         rep = guide.rep if comp or win else 2 if cfg else 1
         vpred = (fused or win_fused) and self.scheduler.config['prediction_type'] == 'v_prediction'
-        if win_fused:
+        if win_fused or win_planned:
             # the window batch: the one persistent buffer (what the graph / plan reads); the canvas does not evict it
             grid = guide.bind(H, W)
             wshape = (B * grid.count, C, grid.h, grid.w)
@@ -538,15 +548,17 @@ class FlexPipeline():
                         latents = latents.clone()
                     else:
                         eps = self._unet_eps(wins, int(t), guide.stacked_embeds(), rep)
-                    coef = self.scheduler.step_coefficients(int(t), 0.0)[:4]
-                    if known is None:
-                        # CFG per window, the average, the DDIM update of the canvas and the next window batch in one launch
-                        guide.step(latents, wins, eps, coef, vpred)
+                    # CFG per window, the average, the update of the canvas, the step noise, the known-region blend of a masked
+                    # request and the next window batch (of the blended canvas) in one launch
+                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                    if win_ms:
+                        self.scheduler.fused_window_step(latents, wins, eps, int(t), B, C, grid.args, guide.blend_code,
+                                                         guide.classifier_free_guidance, guide.guidance, blend,
+                                                         (step_noise, t_start + i) if sde else None)
                     else:
-                        # the blend changes the canvas: step, blend, then the next window batch from the blended canvas
-                        guide.step(latents, None, eps, coef, vpred)
-                        blend_known(latents, i)
-                        guide.gather(latents, wins)
+                        coef = self.scheduler.step_coefficients(int(t), eta if win_noisy else 0.0)
+                        guide.step(latents, wins, eps, coef[:4], vpred, mask=blend, sigma=float(coef[4]) if win_noisy else 0.0,
+                                   step_noise=(step_noise, t_start + i) if win_noisy else None)
                 else:
                     t_index, model_input = t, latents
                     if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling
@@ -563,6 +575,13 @@ class FlexPipeline():
                                                       eps_out=noise_pred)
                         else:
                             ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
+                    elif win_planned:
+                        # guide.noise_pred with the UNet forward from the graph / plan: gather into the persistent window batch,
+                        # replay, the combine-only form of the windowed step
+                        guide.gather(model_input.to(self.device, torch.float32).contiguous(), wins)
+                        eps = self._unet_eps(wins, float(t), guide.stacked_embeds(), rep)
+                        noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
+                        guide.step(None, None, eps, eps_out=noise_pred)
                     else:
                         noise_pred = guide.noise_pred(model_input, t)
                     if takes_noise:

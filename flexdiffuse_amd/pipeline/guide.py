@@ -97,11 +97,14 @@ class WindowedGuide(SimpleGuide):
     whatever latents the guide is handed.  A canvas equal to the window is SimpleGuide, bit for bit.
 
     `noise_pred` is the generic protocol (gather, eager UNet, combine-only fd_window_step_f32), so every scheduler and any
-    caller written against GuideBase works.  Under DDIM with eta = 0 FlexPipeline runs its device loop instead: the window
-    batch is the buffer its graph / launch plan reads, and a step is the UNet replay plus one fd_window_step_f32 (CFG,
-    average, DDIM update of the canvas, the next window batch).  A planned (graph) route for the other schedulers is out of
-    scope: they take the generic route with the eager UNet.  `guidance_rescale` is not supported (its standard deviations
-    would have to span the canvas).'''
+    caller written against GuideBase works.  FlexPipeline runs its device loop instead: the window batch is the buffer its
+    graph / launch plan reads, and under DDIM (eta = 0, or eta > 0 with `pipe.step_noise`), DPM-Solver++ and its SDE form a
+    step is the UNet replay plus ONE launch (fd_window_step_f32, fd_window_ddim_step_f32, fd_window_multistep_step_f32: CFG,
+    average, the update of the canvas, the step noise, the known-region blend of a masked request, the next window batch).
+    The step noise is addressed by the canvas element, so it does not depend on the window grid.  Every other scheduler
+    (PNDM, K-LMS, DDIM eta > 0 on generator noise) takes the planned route: one gather, the UNet replay, the combine-only
+    form, `scheduler.step` -- the bits of the `noise_pred` loop.  `guidance_rescale` is not supported (its standard
+    deviations would have to span the canvas), nor is a CompositeGuide over windows.'''
 
     def __init__(self, encoder, unet, guidance: float, steps: int, clip_embeds: torch.Tensor, *, window=(512, 512),
                  stride=(256, 256), blend: str = 'uniform', guidance_rescale: float = 0.0):
@@ -159,11 +162,19 @@ class WindowedGuide(SimpleGuide):
         return out
 
     def step(self, x: Optional[torch.Tensor], wins: Optional[torch.Tensor], eps: torch.Tensor, coef=(0.0, 1.0, 1.0, 0.0),
-             v_prediction: bool = False, eps_out: Optional[torch.Tensor] = None):
+             v_prediction: bool = False, eps_out: Optional[torch.Tensor] = None, mask=None, sigma: float = 0.0,
+             step_noise=None):
         '''CFG + average of the UNet output `eps` over the window batch (NHWC fp32) into `eps_out` (NCHW fp32 canvas,
         optional) and, given the canvas `x`, its DDIM update in place plus -- given `wins` -- the next window batch:
-        one launch.'''
+        one launch.  With the canvas, optionally in that launch: `sigma` and `step_noise` = (PhiloxNoise, draw), the
+        eta > 0 term sigma z addressed by the canvas element; `mask` = (z0, noise, mask [H W], k1, k2), the known-region
+        blend of masked img2img (the window batch then holds the blended canvas).'''
         B, C, H, W = (x if x is not None else eps_out).shape
+        if x is not None and (mask is not None or sigma):
+            noise, draw = step_noise if step_noise is not None else (None, 0)
+            ops.window_ddim_step(x, wins, eps, B, C, self.grid(H, W).args, self.blend_code, self.classifier_free_guidance,
+                                 self.guidance, coef, v_prediction, mask, float(sigma), noise, int(draw), eps_out)
+            return
         ops.window_step(x, wins, eps, B, C, self.grid(H, W).args, self.blend_code, self.classifier_free_guidance,
                         self.guidance, coef, v_prediction, do_step=x is not None, eps_out=eps_out)
 

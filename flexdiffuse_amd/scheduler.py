@@ -470,8 +470,23 @@ class DPMSolverMultistepScheduler(_Configured):
         self._last = i
 
     def _rescale_noise(self, i: int, co, step_noise) -> dict:
-        '''The noise arguments of the rescaled launch: none for the ODE solver.'''
+        '''The noise arguments of the rescaled and of the windowed launch: none for the ODE solver.'''
         return {}
+
+    def fused_window_step(self, canvas: torch.Tensor, wins: Optional[torch.Tensor], eps_nhwc: torch.Tensor, timestep, B: int,
+                          C: int, grid_args, blend: int, cfg: bool, guidance: float, mask=None, step_noise=None):
+        '''`fused_step` on the canvas of a windowed request (fd_window_multistep_step_f32): `eps_nhwc` is the UNet output over
+        the window batch; one launch takes CFG per window, the average where windows overlap, x0 into the history, the
+        update, the blend of `mask` = (z0, noise, mask [H W], k1, k2) and writes the next window batch into `wins`.  The
+        history is canvas-shaped.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).  A method of its own:
+        `fused_step`'s signature is pinned.'''
+        i = self.step_index(timestep)
+        hist = self._history(canvas)
+        order = self.step_order(i)
+        co = self.step_coefficients(i, order)
+        ops.window_multistep_step(canvas, wins, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C,
+                                  grid_args, blend, cfg, guidance, co[:5], mask, **self._rescale_noise(i, co, step_noise))
+        self._last = i
 
     def fused_rescale_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
                            guidance: float, rescale: float, mask=None, step_noise=None):

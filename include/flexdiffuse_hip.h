@@ -619,6 +619,36 @@ int fd_window_gather_f32(const float* canvas, float* windows, int B, int C, int 
 int fd_window_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, int B, int C, int ld, int H,
                        int W, int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance,
                        float c1, float c2, float c3, float c4, int v_prediction, int do_step, void* stream);
+/* The other schedulers, the step noise and the mask of a windowed request in that same one launch (additive; FD_ABI_VERSION
+ * stays 12).  Both are fronts of fd_window_step_f32's kernel and take its grid, eps_nhwc, blend, cfg and guidance; per canvas
+ * cell (b, y, x) and channel, o the NCHW canvas element ((b C + c) H + y) W + x, every operation a separately rounded fp32 one:
+ *   e as fd_window_step_f32 (-> eps_out, fd_window_ddim_step_f32 only, optional)
+ *   the update: DDIM (fd_cfg_ddim_step_f32's, c1..c4 of step_coefficients(t, eta)) | multistep (fd_cfg_multistep_step_f32's:
+ *     d0 = p x + q e ;  x' = a x + w0 d0 (+ w1 m1[o], m1 != NULL: order 2))
+ *   x' = x' + sn z (sigma | sn != 0): z the counter-based normal stream (fd_philox_normal_f32) of CANVAS element o --
+ *     per = C H W, sample = sample_offset + b, draw, stream 0.  The noise is a function of the canvas element and never of the
+ *     window grid: it equals the fill of a (B, C, H, W) tensor at that element.  sigma | sn == 0: no noise stage, seed,
+ *     sample_offset and draw are ignored.
+ *   m0_out[o] = d0 (multistep; the history holds the noise-free data prediction; m0_out and m1 are canvas-shaped)
+ *   mask != NULL ([H][W] over the canvas, shared by the samples; needs z0 and noise, canvas-shaped):
+ *     x' = the known-region blend of fd_cfg_ddim_masked_step_f32 on (x', z0[o], noise[o], mask[y W + x], k1, k2)
+ *   x[o] = x' ;  windows_out (optional) <- the same, blended value in the cell of every covering window
+ * With neither mask nor sigma fd_window_ddim_step_f32 gives the bits of fd_window_step_f32(do_step = 1); on a one-window grid
+ * both give the bits of fd_cfg_ddim_noise_step_f32 / fd_cfg_multistep_[noise_]step_f32 on the same operands; either equals the
+ * combine-only form followed by that non-windowed step on B C one-channel planes and fd_window_gather_f32.
+ * FD_EINVAL: the grid's errors; NULL x, eps_nhwc or m0_out; m0_out aliasing x or m1; mask without z0 / noise; z0 / noise
+ * aliasing x; eps_out aliasing x; windows_out aliasing any other buffer of the call; with noise, C H W past 2^31, a negative
+ * sample_offset or draw, or sample_offset + B past 2^32. */
+int fd_window_ddim_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, const float* z0,
+                            const float* noise, const float* mask, int B, int C, int ld, int H, int W, int h, int w,
+                            int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance, float c1, float c2,
+                            float c3, float c4, int v_prediction, float k1, float k2, float sigma, uint64_t seed,
+                            int64_t sample_offset, int draw, void* stream);
+int fd_window_multistep_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* m0_out, const float* m1,
+                                 const float* z0, const float* noise, const float* mask, int B, int C, int ld, int H, int W,
+                                 int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance,
+                                 float p, float q, float a, float w0, float w1, float k1, float k2, float sn, uint64_t seed,
+                                 int64_t sample_offset, int draw, void* stream);
 /* Contiguous casts: fp32 -> fp16 rounds to nearest even (overflow to inf from 65520 on), fp16 -> fp32 is exact. */
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
