@@ -1,6 +1,7 @@
 // The per-step arithmetic on the fp32 latents, stated ONCE: classifier-free guidance, the DDIM (eta = 0) update and the
-// known-region blend of masked img2img, and the DPM-Solver++ multistep update.  k_latent_step (step.hip: fd_cfg_ddim_step_f32,
-// fd_cfg_ddim_masked_step_f32, fd_cfg_multistep_step_f32), k_window_step (window.hip), k_composite_step (composite.hip) and
+// known-region blend of masked img2img, the DPM-Solver++ multistep update and the linear multistep updates of PLMS and K-LMS.
+// k_latent_step (step.hip: fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32, fd_cfg_multistep_step_f32,
+// fd_cfg_linear_multistep_step_f32), k_window_step (window.hip), k_composite_step (composite.hip) and
 // k_region_blend (elementwise.hip) all call these, so
 // the product's contract -- those entry points are bit-equal to each other and to an fp32 torch restatement in the same
 // order -- holds by construction.  Every operation is a separately rounded fp32 intrinsic: the library builds with
@@ -9,7 +10,7 @@
 #include "common.h"
 
 // the update a step kernel is instantiated for (k_latent_step, k_window_step)
-enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2 };
+enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2, FD_STEP_LINEAR = 3 };
 
 // a + w (b - a)
 __device__ __forceinline__ float fd_lerp(float a, float b, float w) { return __fadd_rn(a, __fmul_rn(w, __fsub_rn(b, a))); }
@@ -36,6 +37,33 @@ __device__ __forceinline__ float fd_multistep_update(float x, float e, float m1,
     d0 = __fadd_rn(__fmul_rn(co[0], x), __fmul_rn(co[1], e));
     float xn = __fadd_rn(__fmul_rn(co[2], x), __fmul_rn(co[3], d0));
     if (order2) xn = __fadd_rn(xn, __fmul_rn(co[4], m1));
+    return xn;
+}
+
+// PLMS (PNDM without its Runge-Kutta start; Liu et al. 2022, "Pseudo Numerical Methods for Diffusion Models on Manifolds"):
+// E = e (n_prev == 0) | w0 e + w1 h1, then E = 1 E + wk hk for k = 2..n_prev (h: earlier guided eps, newest first) ;
+// x' = cs xs + ce E.  The chain of fd_axpby_f32 launches of PNDMScheduler.step, operation for operation.
+__device__ __forceinline__ float fd_plms_update(float xs, float e, const float (&h)[3], int n_prev, const float (&w)[4], float cs,
+                                                float ce) {
+    float E = e;
+    if (n_prev >= 1) E = __fadd_rn(__fmul_rn(w[0], e), __fmul_rn(w[1], h[0]));
+#pragma unroll
+    for (int k = 2; k <= 3; ++k)
+        if (k <= n_prev) E = __fadd_rn(__fmul_rn(1.f, E), __fmul_rn(w[k], h[k - 1]));
+    return __fadd_rn(__fmul_rn(cs, xs), __fmul_rn(ce, E));
+}
+
+// K-LMS (linear multistep in sigma space), sc = (-sigma, 1/sigma, -1/sigma):  x0 = 1 x + sc0 e ;  d = sc1 x + sc2 x0 (the
+// derivative, the history's next entry) ;  x' = 1 x + c0 d, then x' = 1 x' + ck hk for k = 1..n_prev (h: earlier derivatives,
+// newest first).  The chain of fd_axpby_f32 launches of LMSDiscreteScheduler.step, operation for operation.
+__device__ __forceinline__ float fd_klms_update(float x, float e, const float (&h)[3], int n_prev, const float (&c)[4],
+                                                const float (&sc)[3], float& d) {
+    const float x0 = __fadd_rn(__fmul_rn(1.f, x), __fmul_rn(sc[0], e));
+    d = __fadd_rn(__fmul_rn(sc[1], x), __fmul_rn(sc[2], x0));
+    float xn = __fadd_rn(__fmul_rn(1.f, x), __fmul_rn(c[0], d));
+#pragma unroll
+    for (int k = 1; k <= 3; ++k)
+        if (k <= n_prev) xn = __fadd_rn(__fmul_rn(1.f, xn), __fmul_rn(c[k], h[k - 1]));
     return xn;
 }
 

@@ -1,9 +1,13 @@
-// The per-step update of the NCHW fp32 latents on the device loop: ONE kernel behind five entry points.
+// The per-step update of the NCHW fp32 latents on the device loop: ONE kernel behind these entry points.
 //   fd_cfg_ddim_step_f32         CFG combine (-> eps_out) and, with do_step, the DDIM (eta = 0) update
 //   fd_cfg_ddim_masked_step_f32  masked img2img: that step followed by the known-region blend, or (eps == NULL) the blend
 //                                alone on the x' that x already holds (any scheduler, any guide)
 //   fd_cfg_multistep_step_f32    DPM-Solver++ (2M) (Lu et al. 2022, "DPM-Solver++", Algorithm 2): CFG combine, the data
 //                                prediction m0 = p x + q e -> m0_out, x' = a x + w0 m0 (+ w1 m1: order 2), the blend
+//   fd_cfg_linear_multistep_step_f32   PLMS (PNDMScheduler) and K-LMS (LMSDiscreteScheduler): CFG combine, the history row
+//                                (guided eps | the derivative) -> h_out, the linear multistep update over up to three earlier
+//                                rows (latent_step.h: fd_plms_update, fd_klms_update), the blend, and for K-LMS the next
+//                                step's scaled model input -> x_scaled_out
 //   fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32   the stochastic forms (DDIM eta > 0, SDE-DPM-Solver++):
 //                                the same steps plus x' += sn z, z the counter-based normal stream of philox.h generated
 //                                in the kernel; fd_philox_normal_f32 writes that stream out on its own
@@ -31,6 +35,11 @@ struct FdStepArgs {
     float g, co[5], k1, k2;
     float sn;                  // noise coefficient; 0: no noise stage (nz_addr unused)
     FdNoiseAddr nz_addr;
+    // FD_STEP_LINEAR only (zero elsewhere).  History rows, newest first: m1, h2, h3; the row this step writes: m0_out.
+    const float *h2, *h3, *x_src;
+    float *x_keep, *x_scaled;
+    int form, n_prev;          // form 0: PLMS, lw = w0..w3, la = (cs, ce) | 1: K-LMS, lw = c0..c3, la = (-sigma, 1/sigma, -1/sigma)
+    float lw[4], la[3], ls;    // ls: the factor of x_scaled
 };
 
 // One thread owns V consecutive pixels of one (b, c) plane.  V = 4: HW % 4 == 0 and 16-byte bases, so a group never
@@ -69,6 +78,26 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
             ev[j] = d0;
         }
         fd_stv<V>(a.m0_out + e, ev);
+    } else if constexpr (UPDATE == FD_STEP_LINEAR) {
+        float h[3][V], sv[V];
+        if (a.n_prev >= 1) fd_ldv<V>(a.m1 + e, h[0]);
+        if (a.n_prev >= 2) fd_ldv<V>(a.h2 + e, h[1]);
+        if (a.n_prev >= 3) fd_ldv<V>(a.h3 + e, h[2]);
+        if (a.x_src) fd_ldv<V>(a.x_src + e, sv);
+        if (a.x_keep) fd_stv<V>(a.x_keep + e, xv);
+        if (a.form == 0 && a.m0_out) fd_stv<V>(a.m0_out + e, ev);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float hj[3] = {a.n_prev >= 1 ? h[0][j] : 0.f, a.n_prev >= 2 ? h[1][j] : 0.f, a.n_prev >= 3 ? h[2][j] : 0.f};
+            if (a.form == 0) {
+                xv[j] = fd_plms_update(a.x_src ? sv[j] : xv[j], ev[j], hj, a.n_prev, a.lw, a.la[0], a.la[1]);
+            } else {
+                float d;
+                xv[j] = fd_klms_update(xv[j], ev[j], hj, a.n_prev, a.lw, a.la, d);
+                ev[j] = d;
+            }
+        }
+        if (a.form != 0) fd_stv<V>(a.m0_out + e, ev);
     }
     if constexpr (NOISE) {
         float sv[V];
@@ -81,6 +110,13 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
         for (int j = 0; j < V; ++j) xv[j] = fd_known_blend(xv[j], zv[j], nv[j], mv[j], a.k1, a.k2);
     }
     if (use_x) fd_stv<V>(a.x + e, xv);
+    if constexpr (UPDATE == FD_STEP_LINEAR) {
+        if (a.x_scaled) {                                    // fd_axpby_f32(x, NULL, ls, 0): the next step's model input (K-LMS)
+#pragma unroll
+            for (int j = 0; j < V; ++j) xv[j] = __fadd_rn(__fmul_rn(a.ls, xv[j]), __fmul_rn(0.f, 0.f));
+            fd_stv<V>(a.x_scaled + e, xv);
+        }
+    }
 }
 
 template <int V, int UPDATE, bool NOISE>
@@ -166,13 +202,17 @@ static int fd_latent_step(int update, const FdStepArgs& a, void* stream) {
     uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
     if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
     if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
+    // (the linear forms' pointers; NULL on every other update)
+    bases |= (uintptr_t)a.h2 | (uintptr_t)a.h3 | (uintptr_t)a.x_src | (uintptr_t)a.x_keep | (uintptr_t)a.x_scaled;
     const int noise = update != FD_STEP_NONE && a.sn != 0.f;
     const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
-    static void (*const kernels[2][2][3])(const FdStepArgs) = {
-        {{k_latent_step<1, FD_STEP_NONE, false>, k_latent_step<1, FD_STEP_DDIM, false>, k_latent_step<1, FD_STEP_MULTISTEP, false>},
-         {k_latent_step<4, FD_STEP_NONE, false>, k_latent_step<4, FD_STEP_DDIM, false>, k_latent_step<4, FD_STEP_MULTISTEP, false>}},
-        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true>, k_latent_step<1, FD_STEP_MULTISTEP, true>},
-         {nullptr, k_latent_step<4, FD_STEP_DDIM, true>, k_latent_step<4, FD_STEP_MULTISTEP, true>}}};
+    static void (*const kernels[2][2][4])(const FdStepArgs) = {
+        {{k_latent_step<1, FD_STEP_NONE, false>, k_latent_step<1, FD_STEP_DDIM, false>, k_latent_step<1, FD_STEP_MULTISTEP, false>,
+          k_latent_step<1, FD_STEP_LINEAR, false>},
+         {k_latent_step<4, FD_STEP_NONE, false>, k_latent_step<4, FD_STEP_DDIM, false>, k_latent_step<4, FD_STEP_MULTISTEP, false>,
+          k_latent_step<4, FD_STEP_LINEAR, false>}},
+        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true>, k_latent_step<1, FD_STEP_MULTISTEP, true>, nullptr},
+         {nullptr, k_latent_step<4, FD_STEP_DDIM, true>, k_latent_step<4, FD_STEP_MULTISTEP, true>, nullptr}}};
     const size_t groups = (size_t)a.B * a.C * a.HW / (vec ? 4 : 1);
     hipLaunchKernelGGL(kernels[noise][vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0, (hipStream_t)stream, a);
     FD_CHECK_LAUNCH("k_latent_step");
@@ -221,6 +261,58 @@ extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float*
     const FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
                           guidance, {p, q, a, w0, w1}, k1, k2, 0.f, {}};
     return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+}
+
+// PLMS (form 0) and K-LMS (form 1): CFG, the history write, the linear multistep update over up to three earlier history rows,
+// the blend and (K-LMS) the next step's scaled model input.  Every check precedes the launch.
+extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc, int form, int n_prev, const float* h1,
+                                                const float* h2, const float* h3, float* h_out, float* x_keep_out,
+                                                const float* x_src, float* x_scaled_out, const float* z0,
+                                                const float* noise, const float* mask, int B, int C, int HW, int ld,
+                                                int cfg, float guidance, float w0, float w1, float w2, float w3, float a0,
+                                                float a1, float a2, float scale, float k1, float k2, void* stream) {
+    FD_PLAN(fd_cfg_linear_multistep_step_f32(x, eps_nhwc, form, n_prev, h1, h2, h3, h_out, x_keep_out, x_src, x_scaled_out, z0,
+                                             noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2, w3, a0, a1, a2, scale, k1,
+                                             k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: x or eps_nhwc is null");
+    FD_CHECK_ARG(form == 0 || form == 1, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: form %d is neither 0 (PLMS) nor 1 (K-LMS)", form);
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: sizes");
+    FD_CHECK_ARG(n_prev >= 0 && n_prev <= 3, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: n_prev %d is outside 0..3", n_prev);
+    const float* const rows[3] = {h1, h2, h3};
+    for (int k = 0; k < n_prev; ++k)
+        FD_CHECK_ARG(rows[k], FD_EINVAL, "fd_cfg_linear_multistep_step_f32: history row h%d is null with n_prev %d", k + 1, n_prev);
+    FD_CHECK_ARG(form == 0 || (h_out && !x_src && !x_keep_out), FD_EINVAL,
+                 "fd_cfg_linear_multistep_step_f32: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out");
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_linear_multistep_step_f32: mask without z0 / noise (null)");
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_linear_multistep_step_f32: z0 / noise alias the latents");
+    // the rows the launch reads besides x and eps
+    const float* const reads[6] = {n_prev >= 1 ? h1 : nullptr, n_prev >= 2 ? h2 : nullptr, n_prev >= 3 ? h3 : nullptr, x_src,
+                                   mask ? z0 : nullptr, mask ? noise : nullptr};
+    float* const outs[2] = {h_out, x_keep_out};
+    for (int o = 0; o < 2; ++o) {
+        if (!outs[o]) continue;
+        FD_CHECK_ARG(outs[o] != x, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out / x_keep_out alias the latents");
+        for (int r = 0; r < 6; ++r)
+            FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out / x_keep_out alias a row that is read");
+    }
+    FD_CHECK_ARG(!h_out || h_out != x_keep_out, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out and x_keep_out alias each other");
+    FD_CHECK_ARG(!x_scaled_out || (x_scaled_out != x && x_scaled_out != h_out && x_scaled_out != x_keep_out), FD_EINVAL,
+                 "fd_cfg_linear_multistep_step_f32: x_scaled_out aliases the latents or another output");
+    FdStepArgs s = {x, eps_nhwc, nullptr, h_out, n_prev >= 1 ? h1 : nullptr, z0, noise, mask, B, C, HW, ld, cfg, 0,
+                    guidance, {0.f, 0.f, 0.f, 0.f, 0.f}, k1, k2, 0.f, {}};
+    s.h2 = n_prev >= 2 ? h2 : nullptr;
+    s.h3 = n_prev >= 3 ? h3 : nullptr;
+    s.x_src = x_src;
+    s.x_keep = x_keep_out;
+    s.x_scaled = x_scaled_out;
+    s.form = form;
+    s.n_prev = n_prev;
+    const float lw[4] = {w0, w1, w2, w3}, la[3] = {a0, a1, a2};
+    for (int k = 0; k < 4; ++k) s.lw[k] = lw[k];
+    for (int k = 0; k < 3; ++k) s.la[k] = la[k];
+    s.ls = scale;
+    return fd_latent_step(FD_STEP_LINEAR, s, stream);
 }
 
 // ---- the stochastic forms ------------------------------------------------------------------------------------------

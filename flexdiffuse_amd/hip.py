@@ -90,6 +90,7 @@ _SIGNATURES = {
                                             c_float, c_float, c_float, c_int, c_float, c_float, P]),
     'fd_cfg_multistep_step_f32': (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                           c_float, c_float, c_float, c_float, c_float, c_float, P]),
+    'fd_cfg_linear_multistep_step_f32': (c_int, [P, P, c_int, c_int] + [P] * 10 + [c_int] * 5 + [c_float] * 11 + [P]),
     'fd_philox_normal_f32': (c_int, [P, c_int64, c_int, c_uint64, c_int64, c_int, c_int, P]),
     'fd_cfg_ddim_noise_step_f32': (c_int, [P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                            c_float, c_float, c_float, c_int, c_float, c_float, c_float, c_uint64, c_int64,

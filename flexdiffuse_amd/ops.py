@@ -1126,6 +1126,30 @@ def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Te
              float(coef[3]), float(coef[4]), float(k1), float(k2), hip.stream())
 
 
+def cfg_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, form: int, hist, h_out: Optional[torch.Tensor], B: int,
+                              C: int, HW: int, cfg: bool, guidance: float, weights, coef, mask=None,
+                              x_keep_out: Optional[torch.Tensor] = None, x_src: Optional[torch.Tensor] = None,
+                              x_scaled_out: Optional[torch.Tensor] = None, scale: float = 0.0):
+    '''PLMS (form 0) / K-LMS (form 1) step (fd_cfg_linear_multistep_step_f32), in place on x (NCHW fp32): e = CFG(eps_nhwc);
+    `hist`: the earlier history rows the step reads, newest first (at most 3).  Form 0: e -> h_out, x -> x_keep_out (each when
+    given); E = e | w0 e + w1 h1 (+ wk hk); x' = cs xs + ce E, xs = x_src when given, else x; weights = (w0, ...), coef = (cs, ce).
+    Form 1: d = the derivative at coef = (-sigma, 1/sigma, -1/sigma) -> h_out; x' = x + c0 d (+ ck hk); weights = (c0, ...).
+    Then the known-region blend of mask = (z0, noise, mask [HW], k1, k2), and scale x -> x_scaled_out when given.'''
+    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    hist = list(hist)
+    assert len(hist) <= 3 and len(weights) <= 4 and len(coef) == (3 if form else 2), (len(hist), len(weights), len(coef))
+    _check_f32(B * C * HW, x, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, *hist)
+    _check_f32(HW, mk)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
+    h = [_p(t) for t in hist] + [None] * (3 - len(hist))
+    w = [float(v) for v in weights] + [0.0] * (4 - len(weights))
+    a = [float(v) for v in coef] + [0.0] * (3 - len(coef))
+    hip.call('fd_cfg_linear_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), int(form), len(hist), h[0], h[1], h[2],
+             _p(h_out), _p(x_keep_out), _p(x_src), _p(x_scaled_out), _p(z0), _p(noise), _p(mk), B, C, HW, eps_nhwc.stride(0),
+             int(cfg), float(guidance), w[0], w[1], w[2], w[3], a[0], a[1], a[2], float(scale), float(k1), float(k2),
+             hip.stream())
+
+
 def philox_normal(out: torch.Tensor, per: int, seed: int, sample_offset: int = 0, draw: int = 0, stream: int = 1) -> torch.Tensor:
     '''Fill `out` (fp32, contiguous) with the counter-based normal stream (fd_philox_normal_f32): flat element i is element
     i % per of sample sample_offset + i // per.  The step kernels add the same values (stream 0) without writing them.'''

@@ -18,6 +18,13 @@ DPM-Solver++ (`DPMSolverMultistepScheduler`, beyond the reference's pinned diffu
 loop with fd_cfg_multistep_step_f32 as its one launch after the UNet (CFG, x0, history write, second-order multistep
 update, and the known-region blend of a masked request); a device CompositeGuide takes the planned route below.
 
+PLMS and K-LMS (`PNDMScheduler` -- what the reference's Runner passes, utils.py:70 -- and `LMSDiscreteScheduler`): SimpleGuide
+with the graph or the plan on runs the device loop with fd_cfg_linear_multistep_step_f32 as its one launch after the UNet
+(`fused_lin`: CFG, the history write, the linear multistep update, the known-region blend of a masked request; under K-LMS the
+launch also writes the next step's sigma-scaled model input into the persistent buffer, the unscaled latents being a tensor of
+the call's own).  `fuse_linear_multistep = False`, guidance rescale, `debug=True`, a CompositeGuide or a WindowedGuide keep
+the planned route below; with neither graph nor plan the reference protocol runs.  The same bits on all of them.
+
 Masked img2img (`mask_image=`, beyond the reference; pipeline/inpaint.py): after every step the kept
 region of the latents is put back on the re-noised init latents -- inside the fused step's own launch
 (fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
@@ -72,7 +79,8 @@ import torch
 from .. import hip, ops
 from ..encode.clip import preprocess
 from ..noise import PhiloxNoise
-from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler
+from ..scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler,
+                         PNDMScheduler)
 from .guide import GuideBase, SimpleGuide, WindowedGuide, check_guidance_rescale
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
 
@@ -105,6 +113,11 @@ class StableDiffusionPipelineOutput():
 
 
 class FlexPipeline():
+    # PLMS / K-LMS under a SimpleGuide with graph or plan on: the step is the scheduler's one-launch `fused_step`
+    # (fd_cfg_linear_multistep_step_f32).  False (on the class or an instance): the planned route, the combine-only launch +
+    # `scheduler.step` -- the same bits
+    fuse_linear_multistep = True
+
     def __init__(self, vae, clip, tokenizer, unet, scheduler):
         scheduler = scheduler.set_format('pt')
         # pipeline/flex.py:57-70: a scheduler config that HAS a steps_offset other than 1 is rewritten
@@ -447,15 +460,29 @@ class FlexPipeline():
         # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
         planned = (not fused and not fused_ms and device_guide and hasattr(self.unet, 'forward_nhwc')
                    and (self.use_graph or self.use_plan) and not debug)
+        is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
+        # SimpleGuide + PLMS / K-LMS on that route: the step (CFG, history write, linear multistep update, known-region blend,
+        # K-LMS's next scaled input) is one fd_cfg_linear_multistep_step_f32 launch through `scheduler.fused_step`
+        fused_lin = (planned and simple and not rescale and self.fuse_linear_multistep
+                     and isinstance(self.scheduler, (PNDMScheduler, LMSDiscreteScheduler)))
+        planned = planned and not fused_lin
         # WindowedGuide with any scheduler the windowed loop does not step itself: the same route over the window batch
         win_planned = win and not win_fused and (self.use_graph or self.use_plan) and not debug
         if (fused or fused_ms) and (self.use_graph or self.use_plan) and not debug:
             # persistent latent buffer: the captured UNet graph / recorded plan reads this address
             latents = self.loop_latents(latents)
-        is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
+        lin_scale = lambda j: 1.0 / ((float(self.scheduler.sigmas[j]) ** 2 + 1) ** 0.5)   # noqa: E731 -- pipeline/flex.py:270-274
+        if fused_lin and is_lms:
+            # K-LMS: the persistent buffer holds the SCALED model input (what the graph / plan reads), written by every step's
+            # launch for the next one and by one axpby for the first; the unscaled latents are a tensor of this call's own
+            latents = latents.to(self.device, torch.float32).clone()
+            lin_input = self.loop_latents(ops.axpby(latents, None, lin_scale(t_start), 0.0))
+        elif fused_lin:
+            # PLMS: the latents live in the persistent buffer and are stepped in place
+            latents = self.loop_latents(latents)
         known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
         self._temb_tab = None
-        if (fused or fused_ms or planned or win_fused or win_planned) and hasattr(self.unet, 'time_bias_table'):
+        if (fused or fused_ms or fused_lin or planned or win_fused or win_planned) and hasattr(self.unet, 'time_bias_table'):
             # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
             # instead of three GEMMs per step
             ts = [float(t) for t in self.scheduler.timesteps[t_start:]]
@@ -541,6 +568,19 @@ class FlexPipeline():
                                                   (step_noise, t_start + i))
                     else:
                         self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
+                elif fused_lin:
+                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                    if is_lms:
+                        # the scheduler steps by sigma index; the UNet sees the float timestep and the scaled buffer, which
+                        # this step's launch refills for the next one
+                        eps = self._unet_eps(lin_input, float(t), guide.stacked_embeds(), rep)
+                        last = t_start + i + 1 >= len(self.scheduler.timesteps)
+                        self.scheduler.fused_step(latents, eps, t_start + i, B, C, H * W, cfg, guide.guidance, blend,
+                                                  scaled_out=None if last else lin_input,
+                                                  next_scale=0.0 if last else lin_scale(t_start + i + 1))
+                    else:
+                        eps = self._unet_eps(latents, float(t), guide.stacked_embeds(), rep)
+                        self.scheduler.fused_step(latents, eps, t, B, C, H * W, cfg, guide.guidance, blend)
                 elif win_fused:
                     if debug:
                         temb = self._temb_row(int(t)).expand(wins.shape[0] * rep, -1).contiguous() if self._temb_tab else None

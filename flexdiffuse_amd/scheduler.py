@@ -187,8 +187,15 @@ class DDIMScheduler(_Configured):
 class PNDMScheduler(_Configured):
     '''PLMS branch (skip_prk_steps=True, what Stable Diffusion v1 ships and what the reference's
     `Runner` actually passes, utils.py:70) of diffusers 0.3.0's `PNDMScheduler`, restated
-    from the published algorithm.  PARITY UNPINNED (diffusers is not installed); the linear
-    multistep combinations run on device through fd_axpby_f32.'''
+    from the published algorithm.  PARITY UNPINNED (diffusers is not installed).  `step`: the linear
+    multistep combinations run on device through fd_axpby_f32, one launch each.
+
+    `fused_step` is the same state machine (`counter`, the number of stored eps, the `counter == 1` swap of t / prev,
+    `multistep_weights`, `prev_coefficients`) with classifier-free guidance, the history write, the combination, the update and
+    optionally the known-region blend of masked img2img as ONE fd_cfg_linear_multistep_step_f32 launch (csrc/step.hip), in
+    place on the latents: bit-equal to `step` fed the CFG combine.  Its history is a device buffer fp32 [5][numel] owned by
+    the scheduler: a ring of four guided eps (entry n in slot n % 4, so the slot written is never one of the three read) and
+    the sample the first call keeps for the second.  A request uses `step` or `fused_step`, not both.'''
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085,
                  beta_end: float = 0.012, beta_schedule: str = 'scaled_linear',
                  skip_prk_steps: bool = True, steps_offset: int = 0):
@@ -204,6 +211,8 @@ class PNDMScheduler(_Configured):
         self.num_inference_steps = None
         self._offset = 0
         self.ets, self.counter, self.cur_sample = [], 0, None
+        self._stored = 0                            # fused_step: guided eps written to the ring so far in this request
+        self._hist: Optional[torch.Tensor] = None
 
     def set_format(self, tensor_format='pt'):
         return self
@@ -217,6 +226,7 @@ class PNDMScheduler(_Configured):
         self.timesteps = np.concatenate([base[:-1], base[-2:-1], base[-1:]])[::-1].copy() \
             .astype(np.int64)
         self.ets, self.counter, self.cur_sample = [], 0, None
+        self._stored = 0
 
     def prev_coefficients(self, t: int, t_prev: int):
         a_t = self.alphas_cumprod[t + 1 - self._offset]
@@ -257,6 +267,46 @@ class PNDMScheduler(_Configured):
         self.counter += 1
         return SimpleNamespace(prev_sample=ops.axpby(sample, eps, float(cs), float(ce)))
 
+    def _history(self, x: torch.Tensor) -> torch.Tensor:
+        h = self._hist
+        if h is None or h.shape[1] != x.numel() or h.device != x.device:
+            h = self._hist = torch.empty((5, x.numel()), dtype=torch.float32, device=x.device)
+            self._stored, self.counter = 0, 0
+        return h
+
+    def fused_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
+                   cfg: bool, guidance: float, mask=None):
+        '''`step` as one launch, in place on `latents` (NCHW fp32 [B][C][HW]) from the UNet's NHWC fp32 output: CFG, the guided
+        eps into the ring, the multistep combination, the update; mask = (z0, noise, mask [HW], k1, k2) adds the known-region
+        blend.  Returns the ring slots (written or None, [read, newest first]).'''
+        if self.ets or self.cur_sample is not None:
+            raise RuntimeError('PNDMScheduler: this request already ran `step`; call set_timesteps before `fused_step`')
+        t = int(timestep)
+        ratio = self.config['num_train_timesteps'] // self.num_inference_steps
+        prev = max(t - ratio, 0)
+        ring = self._history(latents)
+        n = self._stored                             # `step`: len(self.ets) before this call, were it never trimmed
+        write = self.counter != 1
+        if not write:
+            prev, t = t, t + ratio
+        stored = n + 1 if write else n
+        keep = src = None
+        if stored == 1 and self.counter == 0:
+            reads, weights, keep = [], (), ring[4]
+        elif stored == 1 and self.counter == 1:
+            reads, weights, src = [(n - 1) % 4], (0.5, 0.5), ring[4]
+        else:
+            weights = self.multistep_weights(min(stored, 4))
+            reads = [(n - k) % 4 for k in range(1, len(weights))]
+        slot = n % 4 if write else None
+        assert slot not in reads
+        cs, ce = self.prev_coefficients(t, prev)
+        ops.cfg_linear_multistep_step(latents, eps_nhwc, 0, [ring[r] for r in reads], None if slot is None else ring[slot], B, C,
+                                      HW, cfg, guidance, weights, (float(cs), float(ce)), mask, x_keep_out=keep, x_src=src)
+        self._stored = stored
+        self.counter += 1
+        return slot, reads
+
     def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
         t = int(timesteps.reshape(-1)[0]) if isinstance(timesteps, torch.Tensor) else int(timesteps)
         a = self.alphas_cumprod[t]
@@ -267,7 +317,12 @@ class PNDMScheduler(_Configured):
 class LMSDiscreteScheduler(_Configured):
     '''K-LMS (linear multistep, order 4) of diffusers 0.3.0, restated from the published
     algorithm.  PARITY UNPINNED.  The pipeline applies the sigma input scaling exactly where
-    the reference does (pipeline/flex.py:236-238, 270-274).'''
+    the reference does (pipeline/flex.py:236-238, 270-274).
+
+    `fused_step`: the same step (`order = min(i + 1, 4)`, `lms_coefficient`) with classifier-free guidance, the derivative, its
+    history write, the update, the known-region blend of a masked request and the next step's scaled model input as ONE
+    fd_cfg_linear_multistep_step_f32 launch, bit-equal to `step` fed the CFG combine.  The history is a device ring fp32
+    [4][numel] owned by the scheduler.  A request uses `step` or `fused_step`, not both.'''
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085,
                  beta_end: float = 0.012, beta_schedule: str = 'scaled_linear'):
         if beta_schedule != 'scaled_linear':
@@ -282,6 +337,8 @@ class LMSDiscreteScheduler(_Configured):
         self.timesteps = np.arange(0, num_train_timesteps)[::-1].copy()
         self.num_inference_steps = None
         self.derivatives = []
+        self._stored = 0                            # fused_step: derivatives written to the ring so far in this request
+        self._hist: Optional[torch.Tensor] = None
 
     def set_format(self, tensor_format='pt'):
         return self
@@ -297,6 +354,7 @@ class LMSDiscreteScheduler(_Configured):
         sig = (1 - frac) * s[low] + frac * s[high]
         self.sigmas = np.concatenate([sig, [0.0]])
         self.derivatives = []
+        self._stored = 0
 
     def lms_coefficient(self, order: int, t: int, current_order: int) -> float:
         from scipy import integrate
@@ -326,6 +384,41 @@ class LMSDiscreteScheduler(_Configured):
         for c, d in zip(coeffs, reversed(self.derivatives)):
             out = ops.axpby(out, d, 1.0, float(c))
         return SimpleNamespace(prev_sample=out)
+
+    def _history(self, x: torch.Tensor) -> torch.Tensor:
+        h = self._hist
+        if h is None or h.shape[1] != x.numel() or h.device != x.device:
+            h = self._hist = torch.empty((4, x.numel()), dtype=torch.float32, device=x.device)
+            self._stored = 0
+        return h
+
+    def fused_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
+                   cfg: bool, guidance: float, mask=None, scaled_out: Optional[torch.Tensor] = None, next_scale: float = 0.0,
+                   order: int = 4):
+        '''`step` as one fd_cfg_linear_multistep_step_f32 launch, in place on the UNSCALED `latents` (NCHW fp32 [B][C][HW]) from
+        the UNet's NHWC fp32 output: CFG, x0, the derivative into the ring (entry n in slot n % 4), the update over the stored
+        derivatives with `lms_coefficient(min(i + 1, order), i, k)`; mask = (z0, noise, mask [HW], k1, k2) adds the known-region
+        blend; `scaled_out` receives next_scale x', the next step's model input (ops.axpby(x', None, next_scale, 0.0)).
+        `timestep` is the index into `sigmas`, as for `step`.  Returns the ring slots (written, [read, newest first]).'''
+        if self.derivatives:
+            raise RuntimeError('LMSDiscreteScheduler: this request already ran `step`; call set_timesteps before `fused_step`')
+        if not 1 <= order <= 4:
+            raise ValueError(f'order {order}: the history ring holds 4 derivatives')
+        i = int(timestep)
+        sigma = float(self.sigmas[i])
+        ring = self._history(latents)
+        n = self._stored
+        held = min(n + 1, order)                    # `step`: len(self.derivatives) after the append and the pop
+        order = min(i + 1, order)
+        # `step` zips `order` coefficients with the derivatives it holds: the shorter list decides
+        coeffs = [self.lms_coefficient(order, i, k) for k in range(min(order, held))]
+        slot, reads = n % 4, [(n - k) % 4 for k in range(1, len(coeffs))]
+        assert slot not in reads
+        ops.cfg_linear_multistep_step(latents, eps_nhwc, 1, [ring[r] for r in reads], ring[slot], B, C, HW, cfg, guidance,
+                                      [float(c) for c in coeffs], (-sigma, 1.0 / sigma, -1.0 / sigma), mask,
+                                      x_scaled_out=scaled_out, scale=next_scale)
+        self._stored = n + 1
+        return slot, reads
 
     def add_noise(self, original: torch.Tensor, noise: torch.Tensor, timesteps) -> torch.Tensor:
         i = int(timesteps.reshape(-1)[0]) if isinstance(timesteps, torch.Tensor) else int(timesteps)

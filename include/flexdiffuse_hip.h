@@ -531,6 +531,30 @@ int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, const float* z0
 int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1, const float* z0,
                               const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
                               float p, float q, float a, float w0, float w1, float k1, float k2, void* stream);
+/* PLMS and K-LMS on the device loop, one launch per step (additive; FD_ABI_VERSION stays 12): replaces, for the scheduler the
+ * reference's Runner passes its pipeline (utils.py:70: PNDM in its PLMS form) and for LMSDiscreteScheduler, the CFG combine
+ * of pipeline/guide.py:59-63 (fd_cfg_ddim_step_f32 without do_step), the chain of fd_axpby_f32 launches of
+ * `scheduler.step` (pipeline/flex.py:280-285), K-LMS's sigma input scaling (pipeline/flex.py:270-274) and the blend-only
+ * launch of a masked request.  Per NCHW element, every operation a separately rounded fp32 one, every scalar the float the
+ * fd_axpby_f32 call it replaces received:
+ *   e = u + g (t - u) (cfg; otherwise the one eps row)
+ *   form 0, PLMS (history rows h1..h3: earlier guided eps, newest first; n_prev of them are read):
+ *     h_out <- e (h_out != NULL) ;  x_keep_out <- x (x_keep_out != NULL) ;  xs = x_src ? x_src : x
+ *     E = e (n_prev == 0) | w0 e + w1 h1, then E = 1 E + wk hk for k = 2..n_prev ;  x' = a0 xs + a1 E     (a0, a1) = (cs, ce)
+ *     (PLMS's second call on the repeated timestep: n_prev = 1, (w0, w1) = (0.5, 0.5), h_out NULL, x_src the kept sample)
+ *   form 1, K-LMS (history rows: earlier derivatives), (a0, a1, a2) = (-sigma, 1/sigma, -1/sigma), (w0..w3) = c0..c3:
+ *     x0 = 1 x + a0 e ;  d = a1 x + a2 x0 ;  h_out <- d ;  x' = 1 x + w0 d, then x' = 1 x' + wk hk for k = 1..n_prev
+ *   mask != NULL: known = k1 z0 + k2 noise ;  x <- x' where m == 1, known where m == 0, known + m (x' - known) otherwise
+ *   x_scaled_out <- scale x + 0 0 (x_scaled_out != NULL: fd_axpby_f32(x, NULL, scale, 0), the next K-LMS model input)
+ * x: NCHW fp32 [B][C][HW], updated in place; every other row has its shape.  eps_nhwc as fd_cfg_ddim_step_f32 reads it.
+ * FD_EINVAL before any launch: x or eps_nhwc NULL; n_prev outside 0..3; one of the first n_prev history rows NULL; h_out or
+ * x_keep_out aliasing x, each other or a row that is read (h1..h3, x_src, z0, noise); x_scaled_out aliasing x; form 1 with
+ * x_src, with x_keep_out or without h_out; the mask rules of fd_cfg_multistep_step_f32. */
+int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc, int form, int n_prev, const float* h1, const float* h2,
+                                     const float* h3, float* h_out, float* x_keep_out, const float* x_src,
+                                     float* x_scaled_out, const float* z0, const float* noise, const float* mask, int B, int C,
+                                     int HW, int ld, int cfg, float guidance, float w0, float w1, float w2, float w3, float a0,
+                                     float a1, float a2, float scale, float k1, float k2, void* stream);
 /* Stochastic sampling on the device loop (additive; FD_ABI_VERSION stays 12): the step noise the reference's
  * scheduler draws when `eta` is forwarded to it (pipeline/flex.py:247-251) comes from a counter-based normal stream
  * generated inside the step kernel, never from a tensor.  Value z of flat element i of a launch:
