@@ -9,7 +9,10 @@ Beyond it: `batch_size = B > 1` (B independent compositions in ONE UNet forward 
 context in rep-major order [uncond]*B [bg]*B [e_1]*B ...) and soft entity masks (weight
 blend * mean of the mask's 8x8 pixel cell per latent cell).  Those requests blend, combine and (in
 FlexPipeline's device loop) take the DDIM step in one launch, fd_composite_step_f32; batch 1 without
-masks keeps the per-entity fd_region_blend_f32 chain.  The style-blend embedding the reference
+masks keeps the per-entity fd_region_blend_f32 chain in `noise_pred`.  FlexPipeline (`fuse_composite`, on by default) runs every
+CompositeGuide, batch 1 included, on its device loop under every scheduler: the entity blend is the source of the guided
+prediction inside the scheduler's own one-launch step (fd_composite_ddim_step_f32, fd_composite_multistep_step_f32,
+fd_composite_linear_multistep_step_f32) -- `entity_rows` hands the schedulers the weight maps.  The style-blend embedding the reference
 computes at composition/guide.py:114-121 is dead code there and is not evaluated here -- unless the
 caller opts in with `style_linear=(l0, l1)`: every prompt block E then gets the two keyframes
 E + omega (S_start - E) and E + omega (S_end - E), omega = linspace(l0, l1, tokens) per token (the reference's
@@ -129,11 +132,27 @@ class CompositeGuide(GuideBase):
             self._wmaps[(H, W)] = w
         return w
 
+    def entity_rows(self, H: int, W: int) -> torch.Tensor:
+        '''`weights(H, W)` as the schedulers' `fused_step(entities=)` takes it: device fp32 [n][H W]; without entities an empty
+        [0][H W] marker, which still selects the rep-major row count.'''
+        w = self.weights(H, W)
+        if w is None:
+            return torch.empty((0, H * W), dtype=torch.float32, device=self.embed_tensor.device)
+        return w.view(w.shape[0], H * W)
+
     def step(self, x: Optional[torch.Tensor], eps: torch.Tensor, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
-             eps_out: Optional[torch.Tensor] = None):
+             eps_out: Optional[torch.Tensor] = None, mask=None, sigma: float = 0.0, step_noise=None):
         '''Blend + CFG of the UNet output `eps` (NHWC fp32, rep-major rows) into `eps_out` (NCHW fp32, optional) and,
-        given `x` (NCHW fp32), the DDIM update of `x` in place: one launch.'''
+        given `x` (NCHW fp32), the DDIM update of `x` in place: one launch.  With `x`, optionally in that launch
+        (fd_composite_ddim_step_f32): `sigma` and `step_noise` = (PhiloxNoise, draw), the eta > 0 term sigma z at C H W
+        elements per sample; `mask` = (z0, noise, mask [H W], k1, k2), the known-region blend of masked img2img.'''
         B, C, H, W = (x if x is not None else eps_out).shape
+        assert not sigma or (x is not None and step_noise is not None), 'sigma needs the latents and a step_noise'
+        if x is not None and (mask is not None or step_noise is not None):
+            noise, draw = step_noise if step_noise is not None else (None, 0)
+            ops.composite_ddim_step(x, eps, self.weights(H, W), B, C, H * W, self.classifier_free_guidance, self.guidance, coef,
+                                    v_prediction, mask, float(sigma), noise, C * H * W, int(draw), eps_out)
+            return
         ops.composite_step(x, eps, self.weights(H, W), B, C, H * W, self.classifier_free_guidance, self.guidance,
                            coef, v_prediction, do_step=x is not None, eps_out=eps_out)
 

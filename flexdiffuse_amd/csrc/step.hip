@@ -11,10 +11,15 @@
 //   fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32   the stochastic forms (DDIM eta > 0, SDE-DPM-Solver++):
 //                                the same steps plus x' += sn z, z the counter-based normal stream of philox.h generated
 //                                in the kernel; fd_philox_normal_f32 writes that stream out on its own
+//   fd_composite_ddim_step_f32, fd_composite_multistep_step_f32, fd_composite_linear_multistep_step_f32   region composition
+//                                (CompositeGuide): the same steps with the guided e formed from E = cfg + 1 + n row blocks
+//                                ([uncond] [background] [entity 0] ...): every entity is blended onto the background by its
+//                                per-pixel weight before the CFG combine (fd_step_group, COMP); n == 0 is the fd_cfg_* sibling
 //   fd_cfg_rescale_ddim_step_f32, fd_cfg_rescale_multistep_step_f32   guidance rescale: all of the above with the guided e
 //                                of each sample multiplied by a factor from two of its standard deviations, computed in the
 //                                step's own launch (k_latent_step_rescale, one workgroup per sample, the same per-group body)
 // Per element, in this order, every operation a separately rounded fp32 one (latent_step.h; no FMA):
+//   (composition: t = bg, then t = t + w_k (entity_k - t) for k ascending wherever w_k != 0) ;
 //   e = u + g (t - u) (cfg; otherwise the one eps row) ;  e = f_b e (rescaled forms) -> eps_out ;  the update ;  + sn z (sn != 0) ;  -> m0_out ;
 //   the blend (mask) ;  -> x
 // so the entry points are bit-equal to each other wherever they overlap (an all-ones mask is the plain step, an
@@ -40,6 +45,10 @@ struct FdStepArgs {
     float *x_keep, *x_scaled;
     int form, n_prev;          // form 0: PLMS, lw = w0..w3, la = (cs, ce) | 1: K-LMS, lw = c0..c3, la = (-sigma, 1/sigma, -1/sigma)
     float lw[4], la[3], ls;    // ls: the factor of x_scaled
+    // the composite forms only (NULL / 0 elsewhere): fp32 [n_ent][HW] blend weights, shared by the B samples; eps then holds
+    // cfg + 1 + n_ent blocks of B HW rows in rep-major order
+    const float* wmap;
+    int n_ent;
 };
 
 // One thread owns V consecutive pixels of one (b, c) plane.  V = 4: HW % 4 == 0 and 16-byte bases, so a group never
@@ -47,8 +56,10 @@ struct FdStepArgs {
 // V = 4: per % 4 == 0 too, so a group is one Philox block): x' += sn z between the update and the blend.
 // fd_step_group is the whole step of the group whose first pixel is NCHW element e = (b, c, p), the one body of
 // k_latent_step and k_latent_step_rescale; RESCALE: the guided output is multiplied by the sample's factor f between the CFG
-// combine and everything after it.
-template <int V, int UPDATE, bool NOISE, bool RESCALE>
+// combine and everything after it.  COMP (n_ent > 0): the conditional value is the background row with every entity lerped onto
+// it in ascending order wherever its weight is not 0 (k_composite_step's arithmetic: no exact branch for a weight of 1); the
+// V weights of an entity are one float4 (HW % 4 == 0 keeps wmap + k HW + p aligned).
+template <int V, int UPDATE, bool NOISE, bool RESCALE, bool COMP = false>
 __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int b, int c, int p, bool use_x, float f) {
     float xv[V], ev[V], hv[V], zv[V], nv[V], mv[V];
     if (use_x) fd_ldv<V>(a.x + e, xv);
@@ -58,7 +69,26 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
         fd_ldv<V>(a.nz + e, nv);
         fd_ldv<V>(a.mask + p, mv);
     }
-    if (a.eps) {
+    if constexpr (COMP) {
+        const size_t blk = (size_t)a.B * a.HW * a.ld;        // elements per block of B samples
+        const size_t row = ((size_t)b * a.HW + p) * a.ld + c;
+        const float* bg = a.eps + (a.cfg ? blk : 0);
+        float wv[V];
+#pragma unroll
+        for (int j = 0; j < V; ++j) ev[j] = bg[row + (size_t)j * a.ld];
+        for (int k = 0; k < a.n_ent; ++k) {
+            fd_ldv<V>(a.wmap + (size_t)k * a.HW + p, wv);
+            const float* ent = bg + (size_t)(k + 1) * blk + row;
+#pragma unroll
+            for (int j = 0; j < V; ++j)
+                if (wv[j] != 0.f) ev[j] = fd_lerp(ev[j], ent[(size_t)j * a.ld], wv[j]);     // 0: exactly what it held
+        }
+        if (a.cfg) {
+#pragma unroll
+            for (int j = 0; j < V; ++j) ev[j] = fd_cfg_mix(a.eps[row + (size_t)j * a.ld], ev[j], a.g);
+        }
+        if (a.eps_out) fd_stv<V>(a.eps_out + e, ev);
+    } else if (a.eps) {
 #pragma unroll
         for (int j = 0; j < V; ++j) {
             const size_t row = ((size_t)b * a.HW + p + j) * a.ld + c;
@@ -119,7 +149,7 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
     }
 }
 
-template <int V, int UPDATE, bool NOISE>
+template <int V, int UPDATE, bool NOISE, bool COMP = false>
 __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
     const size_t groups = (size_t)a.B * a.C * a.HW / V;
     const bool use_x = UPDATE != FD_STEP_NONE || a.mask;     // CFG combine alone (-> eps_out): x may be NULL
@@ -129,7 +159,7 @@ __global__ __launch_bounds__(256) void k_latent_step(const FdStepArgs a) {
         const size_t r = e / a.HW;
         const int c = r % a.C;
         const int b = r / a.C;
-        fd_step_group<V, UPDATE, NOISE, false>(a, e, b, c, p, use_x, 1.f);
+        fd_step_group<V, UPDATE, NOISE, false, COMP>(a, e, b, c, p, use_x, 1.f);
     }
 }
 
@@ -197,15 +227,24 @@ __global__ __launch_bounds__(FD_RESCALE_THREADS) void k_latent_step_rescale(cons
 }
 
 // V = 4 when HW % 4 == 0 (with noise: per % 4 == 0 too) and every NCHW pointer the kernel will touch is 16-byte aligned,
-// else V = 1; grid; launch.  sn == 0 launches the kernels without the noise stage: today's bits.
+// else V = 1; grid; launch.  sn == 0 launches the kernels without the noise stage: today's bits.  n_ent > 0 launches the
+// COMP instantiations (the weight maps join the aligned pointers); n_ent == 0 the kernels every fd_cfg_* entry point launches.
 static int fd_latent_step(int update, const FdStepArgs& a, void* stream) {
     uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
     if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
     if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
     // (the linear forms' pointers; NULL on every other update)
     bases |= (uintptr_t)a.h2 | (uintptr_t)a.h3 | (uintptr_t)a.x_src | (uintptr_t)a.x_keep | (uintptr_t)a.x_scaled;
+    if (a.n_ent > 0) bases |= (uintptr_t)a.wmap;
     const int noise = update != FD_STEP_NONE && a.sn != 0.f;
     const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
+    static void (*const comp_kernels[2][2][4])(const FdStepArgs) = {
+        {{nullptr, k_latent_step<1, FD_STEP_DDIM, false, true>, k_latent_step<1, FD_STEP_MULTISTEP, false, true>,
+          k_latent_step<1, FD_STEP_LINEAR, false, true>},
+         {nullptr, k_latent_step<4, FD_STEP_DDIM, false, true>, k_latent_step<4, FD_STEP_MULTISTEP, false, true>,
+          k_latent_step<4, FD_STEP_LINEAR, false, true>}},
+        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true, true>, k_latent_step<1, FD_STEP_MULTISTEP, true, true>, nullptr},
+         {nullptr, k_latent_step<4, FD_STEP_DDIM, true, true>, k_latent_step<4, FD_STEP_MULTISTEP, true, true>, nullptr}}};
     static void (*const kernels[2][2][4])(const FdStepArgs) = {
         {{k_latent_step<1, FD_STEP_NONE, false>, k_latent_step<1, FD_STEP_DDIM, false>, k_latent_step<1, FD_STEP_MULTISTEP, false>,
           k_latent_step<1, FD_STEP_LINEAR, false>},
@@ -214,7 +253,8 @@ static int fd_latent_step(int update, const FdStepArgs& a, void* stream) {
         {{nullptr, k_latent_step<1, FD_STEP_DDIM, true>, k_latent_step<1, FD_STEP_MULTISTEP, true>, nullptr},
          {nullptr, k_latent_step<4, FD_STEP_DDIM, true>, k_latent_step<4, FD_STEP_MULTISTEP, true>, nullptr}}};
     const size_t groups = (size_t)a.B * a.C * a.HW / (vec ? 4 : 1);
-    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL((a.n_ent > 0 ? comp_kernels : kernels)[noise][vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0,
+                       (hipStream_t)stream, a);
     FD_CHECK_LAUNCH("k_latent_step");
     return FD_OK;
 }
@@ -265,40 +305,46 @@ extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float*
 
 // PLMS (form 0) and K-LMS (form 1): CFG, the history write, the linear multistep update over up to three earlier history rows,
 // the blend and (K-LMS) the next step's scaled model input.  Every check precedes the launch.
-extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc, int form, int n_prev, const float* h1,
-                                                const float* h2, const float* h3, float* h_out, float* x_keep_out,
-                                                const float* x_src, float* x_scaled_out, const float* z0,
-                                                const float* noise, const float* mask, int B, int C, int HW, int ld,
-                                                int cfg, float guidance, float w0, float w1, float w2, float w3, float a0,
-                                                float a1, float a2, float scale, float k1, float k2, void* stream) {
-    FD_PLAN(fd_cfg_linear_multistep_step_f32(x, eps_nhwc, form, n_prev, h1, h2, h3, h_out, x_keep_out, x_src, x_scaled_out, z0,
-                                             noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2, w3, a0, a1, a2, scale, k1,
-                                             k2, fd_s_));
-    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: x or eps_nhwc is null");
-    FD_CHECK_ARG(form == 0 || form == 1, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: form %d is neither 0 (PLMS) nor 1 (K-LMS)", form);
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: sizes");
-    FD_CHECK_ARG(n_prev >= 0 && n_prev <= 3, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: n_prev %d is outside 0..3", n_prev);
+// the checks the composite fronts add to their siblings'; eps_nhwc then holds (cfg + 1 + n_entities) B HW rows
+static int fd_composite_args(const char* who, const float* weights, int n_entities) {
+    FD_CHECK_ARG(n_entities >= 0, FD_EINVAL, "%s: n_entities %d is negative", who, n_entities);
+    FD_CHECK_ARG(n_entities == 0 || weights, FD_EINVAL, "%s: weights are null with n_entities %d", who, n_entities);
+    return FD_OK;
+}
+
+// the body of fd_cfg_linear_multistep_step_f32 and of its composite front (weights, n_entities: NULL, 0 for the first)
+static int fd_linear_multistep_step(const char* who, float* x, const float* eps_nhwc, const float* weights, int n_entities,
+                                    int form, int n_prev, const float* h1, const float* h2, const float* h3, float* h_out,
+                                    float* x_keep_out, const float* x_src, float* x_scaled_out, const float* z0,
+                                    const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
+                                    float guidance, float w0, float w1, float w2, float w3, float a0, float a1, float a2,
+                                    float scale, float k1, float k2, void* stream) {
+    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "%s: x or eps_nhwc is null", who);
+    FD_CHECK_ARG(form == 0 || form == 1, FD_EINVAL, "%s: form %d is neither 0 (PLMS) nor 1 (K-LMS)", who, form);
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
+    FD_CHECK_ARG(n_prev >= 0 && n_prev <= 3, FD_EINVAL, "%s: n_prev %d is outside 0..3", who, n_prev);
     const float* const rows[3] = {h1, h2, h3};
     for (int k = 0; k < n_prev; ++k)
-        FD_CHECK_ARG(rows[k], FD_EINVAL, "fd_cfg_linear_multistep_step_f32: history row h%d is null with n_prev %d", k + 1, n_prev);
+        FD_CHECK_ARG(rows[k], FD_EINVAL, "%s: history row h%d is null with n_prev %d", who, k + 1, n_prev);
     FD_CHECK_ARG(form == 0 || (h_out && !x_src && !x_keep_out), FD_EINVAL,
-                 "fd_cfg_linear_multistep_step_f32: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_linear_multistep_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_linear_multistep_step_f32: z0 / noise alias the latents");
+                 "%s: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out", who);
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
     // the rows the launch reads besides x and eps
     const float* const reads[6] = {n_prev >= 1 ? h1 : nullptr, n_prev >= 2 ? h2 : nullptr, n_prev >= 3 ? h3 : nullptr, x_src,
                                    mask ? z0 : nullptr, mask ? noise : nullptr};
     float* const outs[2] = {h_out, x_keep_out};
     for (int o = 0; o < 2; ++o) {
         if (!outs[o]) continue;
-        FD_CHECK_ARG(outs[o] != x, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out / x_keep_out alias the latents");
+        FD_CHECK_ARG(outs[o] != x, FD_EINVAL, "%s: h_out / x_keep_out alias the latents", who);
         for (int r = 0; r < 6; ++r)
-            FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out / x_keep_out alias a row that is read");
+            FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "%s: h_out / x_keep_out alias a row that is read", who);
     }
-    FD_CHECK_ARG(!h_out || h_out != x_keep_out, FD_EINVAL, "fd_cfg_linear_multistep_step_f32: h_out and x_keep_out alias each other");
+    FD_CHECK_ARG(!h_out || h_out != x_keep_out, FD_EINVAL, "%s: h_out and x_keep_out alias each other", who);
     FD_CHECK_ARG(!x_scaled_out || (x_scaled_out != x && x_scaled_out != h_out && x_scaled_out != x_keep_out), FD_EINVAL,
-                 "fd_cfg_linear_multistep_step_f32: x_scaled_out aliases the latents or another output");
+                 "%s: x_scaled_out aliases the latents or another output", who);
+    const int rc = fd_composite_args(who, weights, n_entities);
+    if (rc != FD_OK) return rc;
     FdStepArgs s = {x, eps_nhwc, nullptr, h_out, n_prev >= 1 ? h1 : nullptr, z0, noise, mask, B, C, HW, ld, cfg, 0,
                     guidance, {0.f, 0.f, 0.f, 0.f, 0.f}, k1, k2, 0.f, {}};
     s.h2 = n_prev >= 2 ? h2 : nullptr;
@@ -312,7 +358,24 @@ extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc,
     for (int k = 0; k < 4; ++k) s.lw[k] = lw[k];
     for (int k = 0; k < 3; ++k) s.la[k] = la[k];
     s.ls = scale;
+    s.wmap = weights;
+    s.n_ent = n_entities;
     return fd_latent_step(FD_STEP_LINEAR, s, stream);
+}
+
+extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc, int form, int n_prev, const float* h1,
+                                                const float* h2, const float* h3, float* h_out, float* x_keep_out,
+                                                const float* x_src, float* x_scaled_out, const float* z0,
+                                                const float* noise, const float* mask, int B, int C, int HW, int ld,
+                                                int cfg, float guidance, float w0, float w1, float w2, float w3, float a0,
+                                                float a1, float a2, float scale, float k1, float k2, void* stream) {
+    FD_PLAN(fd_cfg_linear_multistep_step_f32(x, eps_nhwc, form, n_prev, h1, h2, h3, h_out, x_keep_out, x_src, x_scaled_out, z0,
+                                             noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2, w3, a0, a1, a2, scale, k1,
+                                             k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    return fd_linear_multistep_step("fd_cfg_linear_multistep_step_f32", x, eps_nhwc, nullptr, 0, form, n_prev, h1, h2, h3, h_out,
+                                    x_keep_out, x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2,
+                                    w3, a0, a1, a2, scale, k1, k2, stream);
 }
 
 // ---- the stochastic forms ------------------------------------------------------------------------------------------
@@ -337,6 +400,29 @@ extern "C" int fd_cfg_ddim_noise_step_f32(float* x, const float* eps_nhwc, const
     return fd_latent_step(FD_STEP_DDIM, a, stream);
 }
 
+// the body of fd_cfg_multistep_noise_step_f32 and of the composite front (weights, n_entities: NULL, 0 for the first)
+static int fd_multistep_noise_step(const char* who, float* x, const float* eps_nhwc, const float* weights, int n_entities,
+                                   float* m0_out, const float* m1, const float* z0, const float* noise, const float* mask,
+                                   int B, int C, int HW, int ld, int cfg, float guidance, float p, float q, float a, float w0,
+                                   float w1, float k1, float k2, float sn, uint64_t seed, int64_t sample_offset, int per,
+                                   int draw, void* stream) {
+    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "%s: x, eps_nhwc or m0_out is null", who);
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
+    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "%s: m0_out aliases the latents or m1", who);
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
+    const int rw = fd_composite_args(who, weights, n_entities);
+    if (rw != FD_OK) return rw;
+    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
+                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
+    const int rc = fd_noise_addr(who, seed, sample_offset, per, draw, 0,
+                                 (unsigned long long)B * C * HW, &s.nz_addr);
+    if (rc != FD_OK) return rc;
+    s.wmap = weights;
+    s.n_ent = n_entities;
+    return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+}
+
 extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
                                                const float* z0, const float* noise, const float* mask, int B, int C,
                                                int HW, int ld, int cfg, float guidance, float p, float q, float a,
@@ -346,17 +432,68 @@ extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, 
     FD_PLAN(fd_cfg_multistep_noise_step_f32(x, eps_nhwc, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, guidance, p, q,
                                             a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: x, eps_nhwc or m0_out is null");
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: sizes");
-    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_cfg_multistep_noise_step_f32: m0_out aliases the latents or m1");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_multistep_noise_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_multistep_noise_step_f32: z0 / noise alias the latents");
-    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
-                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
-    const int rc = fd_noise_addr("fd_cfg_multistep_noise_step_f32", seed, sample_offset, per, draw, 0,
-                                 (unsigned long long)B * C * HW, &s.nz_addr);
-    if (rc != FD_OK) return rc;
-    return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+    return fd_multistep_noise_step("fd_cfg_multistep_noise_step_f32", x, eps_nhwc, nullptr, 0, m0_out, m1, z0, noise, mask, B, C,
+                                   HW, ld, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, stream);
+}
+
+// ---- the composite forms ---------------------------------------------------------------------------------------------
+// Each is the sibling's step with the entity blend as the source of the guided e (fd_step_group, COMP): eps_nhwc holds
+// (cfg + 1 + n_entities) B HW rows in the rep-major order of fd_composite_step_f32, weights fp32 [n_entities][HW].
+// n_entities == 0: the sibling's kernel and bits.
+extern "C" int fd_composite_ddim_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities,
+                                          float* eps_out, const float* z0, const float* noise, const float* mask, int B, int C,
+                                          int HW, int ld, int cfg, float guidance, float c1, float c2, float c3, float c4,
+                                          int v_prediction, float k1, float k2, float sigma, uint64_t seed,
+                                          int64_t sample_offset, int per, int draw, void* stream) {
+    FD_PLAN(fd_composite_ddim_step_f32(x, eps_nhwc, weights, n_entities, eps_out, z0, noise, mask, B, C, HW, ld, cfg, guidance,
+                                       c1, c2, c3, c4, v_prediction, k1, k2, sigma, seed, sample_offset, per, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    const char* const who = "fd_composite_ddim_step_f32";
+    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "%s: x or eps_nhwc is null", who);
+    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
+    const int rw = fd_composite_args(who, weights, n_entities);
+    if (rw != FD_OK) return rw;
+    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
+    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
+    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "%s: eps_out aliases the latents", who);
+    FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
+                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
+    if (sigma != 0.f) {
+        const int rc = fd_noise_addr(who, seed, sample_offset, per, draw, 0, (unsigned long long)B * C * HW, &a.nz_addr);
+        if (rc != FD_OK) return rc;
+    }
+    a.wmap = weights;
+    a.n_ent = n_entities;
+    return fd_latent_step(FD_STEP_DDIM, a, stream);
+}
+
+extern "C" int fd_composite_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities,
+                                               float* m0_out, const float* m1, const float* z0, const float* noise,
+                                               const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
+                                               float p, float q, float a, float w0, float w1, float k1, float k2, float sn,
+                                               uint64_t seed, int64_t sample_offset, int per, int draw, void* stream) {
+    FD_PLAN(fd_composite_multistep_step_f32(x, eps_nhwc, weights, n_entities, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg,
+                                            guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    return fd_multistep_noise_step("fd_composite_multistep_step_f32", x, eps_nhwc, weights, n_entities, m0_out, m1, z0, noise, mask,
+                                   B, C, HW, ld, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw,
+                                   stream);
+}
+
+extern "C" int fd_composite_linear_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities,
+                                                      int form, int n_prev, const float* h1, const float* h2, const float* h3,
+                                                      float* h_out, float* x_keep_out, const float* x_src, float* x_scaled_out,
+                                                      const float* z0, const float* noise, const float* mask, int B, int C,
+                                                      int HW, int ld, int cfg, float guidance, float w0, float w1, float w2,
+                                                      float w3, float a0, float a1, float a2, float scale, float k1, float k2,
+                                                      void* stream) {
+    FD_PLAN(fd_composite_linear_multistep_step_f32(x, eps_nhwc, weights, n_entities, form, n_prev, h1, h2, h3, h_out, x_keep_out,
+                                                   x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2,
+                                                   w3, a0, a1, a2, scale, k1, k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    return fd_linear_multistep_step("fd_composite_linear_multistep_step_f32", x, eps_nhwc, weights, n_entities, form, n_prev, h1,
+                                    h2, h3, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance,
+                                    w0, w1, w2, w3, a0, a1, a2, scale, k1, k2, stream);
 }
 
 // ---- the rescaled forms ----------------------------------------------------------------------------------------------

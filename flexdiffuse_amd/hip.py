@@ -104,6 +104,12 @@ _SIGNATURES = {
     'fd_cfg_rescale_multistep_step_f32': (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float,
                                                   c_float, c_float, c_float, c_float, c_float, c_float, c_float, c_float,
                                                   c_uint64, c_int64, c_int, P]),
+    'fd_composite_ddim_step_f32': (c_int, [P, P, P, c_int, P, P, P, P] + [c_int] * 5 + [c_float] * 5 + [c_int]
+                                   + [c_float] * 3 + [c_uint64, c_int64, c_int, c_int, P]),
+    'fd_composite_multistep_step_f32': (c_int, [P, P, P, c_int, P, P, P, P, P] + [c_int] * 5 + [c_float] * 9
+                                        + [c_uint64, c_int64, c_int, c_int, P]),
+    'fd_composite_linear_multistep_step_f32': (c_int, [P, P, P, c_int, c_int, c_int] + [P] * 10 + [c_int] * 5
+                                               + [c_float] * 11 + [P]),
     'fd_lerp_f16': (c_int, [P, P, P, c_int64, c_float, P]),
     'fd_xattn_fold_rows_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'fd_window_gather_f32': (c_int, [P, P] + [c_int] * 10 + [P]),

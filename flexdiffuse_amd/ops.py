@@ -1251,6 +1251,74 @@ def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: O
              float(coef[3]), int(v_prediction), int(do_step), hip.stream())
 
 
+def _composite_rows(eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, HW: int, cfg: bool) -> int:
+    '''The checks the composite step fronts share: weights fp32 [n][HW] (None or n == 0: no entity), eps_nhwc at least
+    (cfg + 1 + n) B HW rows.  Returns n.'''
+    n = 0 if weights is None else int(weights.shape[0])
+    if n:
+        _check_f32(n * HW, weights)
+    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * HW, C)
+    return n
+
+
+def composite_ddim_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, HW: int,
+                        cfg: bool, guidance: float, coef, v_prediction: bool = False, mask=None, sigma: float = 0.0, noise=None,
+                        per: int = 0, draw: int = 0, eps_out: Optional[torch.Tensor] = None):
+    '''CompositeGuide DDIM step (fd_composite_ddim_step_f32), in place on x (NCHW fp32): `composite_step`'s blend + CFG of
+    eps_nhwc [(cfg + 1 + n) * B * HW][ld] (-> eps_out when given), the DDIM update, x' += sigma z (sigma != 0: z the stream of
+    `noise`, a `PhiloxNoise`, at `per` elements per sample and `draw`) and, with mask = (z0, noise, mask [HW], k1, k2), the
+    known-region blend of `cfg_ddim_masked_step` -- one launch.  Neither: the bits of `composite_step`.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    n = _composite_rows(eps_nhwc, weights, B, C, HW, cfg)
+    _check_f32(B * C * HW, x, eps_out, z0, nz)
+    _check_f32(HW, mk)
+    assert not sigma or noise is not None, 'sigma without a PhiloxNoise'
+    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+    hip.call('fd_composite_ddim_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights) if n else None, n, _p(eps_out),
+             _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]),
+             float(coef[2]), float(coef[3]), int(v_prediction), float(k1), float(k2), float(sigma), seed, offset,
+             int(per) if per else C * HW, int(draw), hip.stream())
+
+
+def composite_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], m0_out: torch.Tensor,
+                             m1: Optional[torch.Tensor], B: int, C: int, HW: int, cfg: bool, guidance: float, coef, mask=None,
+                             sn: float = 0.0, noise=None, per: int = 0, draw: int = 0):
+    '''CompositeGuide DPM-Solver++ step (fd_composite_multistep_step_f32): `cfg_multistep_step` (sn != 0:
+    `cfg_multistep_noise_step`) on the blend + CFG of `composite_step`'s rows -- one launch.'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    n = _composite_rows(eps_nhwc, weights, B, C, HW, cfg)
+    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
+    _check_f32(HW, mk)
+    assert not sn or noise is not None, 'sn without a PhiloxNoise'
+    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+    hip.call('fd_composite_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights) if n else None, n,
+             m0_out.data_ptr(), _p(m1), _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance),
+             float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn),
+             seed, offset, int(per) if per else C * HW, int(draw), hip.stream())
+
+
+def composite_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights_map: Optional[torch.Tensor], form: int,
+                                    hist, h_out: Optional[torch.Tensor], B: int, C: int, HW: int, cfg: bool, guidance: float,
+                                    weights, coef, mask=None, x_keep_out: Optional[torch.Tensor] = None,
+                                    x_src: Optional[torch.Tensor] = None, x_scaled_out: Optional[torch.Tensor] = None,
+                                    scale: float = 0.0):
+    '''CompositeGuide PLMS / K-LMS step (fd_composite_linear_multistep_step_f32): `cfg_linear_multistep_step`, argument for
+    argument, on the blend + CFG of `composite_step`'s rows with the entity maps `weights_map` [n][HW] -- one launch.'''
+    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    hist = list(hist)
+    assert len(hist) <= 3 and len(weights) <= 4 and len(coef) == (3 if form else 2), (len(hist), len(weights), len(coef))
+    n = _composite_rows(eps_nhwc, weights_map, B, C, HW, cfg)
+    _check_f32(B * C * HW, x, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, *hist)
+    _check_f32(HW, mk)
+    h = [_p(t) for t in hist] + [None] * (3 - len(hist))
+    w = [float(v) for v in weights] + [0.0] * (4 - len(weights))
+    a = [float(v) for v in coef] + [0.0] * (3 - len(coef))
+    hip.call('fd_composite_linear_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights_map) if n else None, n,
+             int(form), len(hist), h[0], h[1], h[2], _p(h_out), _p(x_keep_out), _p(x_src), _p(x_scaled_out), _p(z0), _p(noise),
+             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), w[0], w[1], w[2], w[3], a[0], a[1], a[2],
+             float(scale), float(k1), float(k2), hip.stream())
+
+
 def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, grid):
     '''Canvas (B, C, H, W) -> window batch (B Wn, C, h, w), both NCHW fp32 (fd_window_gather_f32).  grid: the plain ints
     (H, W, h, w, stride_y, stride_x, ny, nx) of `windows.WindowGrid.args`; the kernel restates the offsets.'''

@@ -16,14 +16,22 @@ work.  Same kernels, same order, bit-identical results in all three modes.
 
 DPM-Solver++ (`DPMSolverMultistepScheduler`, beyond the reference's pinned diffusers): SimpleGuide runs the same device
 loop with fd_cfg_multistep_step_f32 as its one launch after the UNet (CFG, x0, history write, second-order multistep
-update, and the known-region blend of a masked request); a device CompositeGuide takes the planned route below.
+update, and the known-region blend of a masked request).
 
 PLMS and K-LMS (`PNDMScheduler` -- what the reference's Runner passes, utils.py:70 -- and `LMSDiscreteScheduler`): SimpleGuide
 with the graph or the plan on runs the device loop with fd_cfg_linear_multistep_step_f32 as its one launch after the UNet
 (`fused_lin`: CFG, the history write, the linear multistep update, the known-region blend of a masked request; under K-LMS the
 launch also writes the next step's sigma-scaled model input into the persistent buffer, the unscaled latents being a tensor of
-the call's own).  `fuse_linear_multistep = False`, guidance rescale, `debug=True`, a CompositeGuide or a WindowedGuide keep
+the call's own).  `fuse_linear_multistep = False`, guidance rescale, `debug=True` or a WindowedGuide keep
 the planned route below; with neither graph nor plan the reference protocol runs.  The same bits on all of them.
+
+Composition under every scheduler (`fuse_composite`, default True): every CompositeGuide whose `noise_pred` is the class's own --
+batch 1 with plain rectangles included -- runs on these loops with the entity blend as the source of the guided prediction inside
+the step's one launch: fd_composite_ddim_step_f32 (DDIM with a mask image, or eta > 0 on `pipe.step_noise`),
+fd_composite_multistep_step_f32 (DPM-Solver++ and its SDE form, `scheduler.fused_composite_step`),
+fd_composite_linear_multistep_step_f32 (PLMS and K-LMS, `scheduler.fused_step(entities=)`).  False restores the earlier routes:
+the device loop for a batched or masked composite under DDIM at eta = 0 only (+ a blend-only launch with a mask image), the
+planned route under every other scheduler, `guide.noise_pred` for batch 1.  The route table is DESIGN.md sec. 7.4.
 
 Masked img2img (`mask_image=`, beyond the reference; pipeline/inpaint.py): after every step the kept
 region of the latents is put back on the re-noised init latents -- inside the fused step's own launch
@@ -117,6 +125,13 @@ class FlexPipeline():
     # (fd_cfg_linear_multistep_step_f32).  False (on the class or an instance): the planned route, the combine-only launch +
     # `scheduler.step` -- the same bits
     fuse_linear_multistep = True
+    # CompositeGuide on the device loop under every scheduler: any CompositeGuide (batch 1 with plain rectangles included) reads
+    # the graph / plan and the request's time-embedding table, and its step -- the entity blend, CFG, the update, the step noise,
+    # the history write, the known-region blend -- is ONE launch (fd_composite_step_f32, fd_composite_ddim_step_f32,
+    # fd_composite_multistep_step_f32, fd_composite_linear_multistep_step_f32).  False (on the class or an instance): only a
+    # batched or masked composite under DDIM (eta = 0) steps on the device, with a second blend-only launch for a masked
+    # request; every other scheduler takes the planned route and batch 1 `guide.noise_pred` -- the same bits
+    fuse_composite = True
 
     def __init__(self, vae, clip, tokenizer, unet, scheduler):
         scheduler = scheduler.set_format('pt')
@@ -420,10 +435,12 @@ class FlexPipeline():
         latents = init_latents.contiguous()
         all_latents = [init_latents] if debug else None
         from ..composition.guide import CompositeGuide
-        # CompositeGuide with batched samples or masks: blend + CFG (+ DDIM update) in one launch per step after the
-        # UNet forward over its E context blocks (the batch-1 rectangle path stays on the generic protocol)
-        comp = (type(guide).noise_pred is CompositeGuide.noise_pred and getattr(guide, 'on_device', False)
+        # CompositeGuide: blend + CFG + the scheduler's update in one launch per step after the UNet forward over its E context
+        # blocks (`fuse_composite` off: batched samples or masks only, the batch-1 rectangle path on the generic protocol)
+        comp_fused = bool(self.fuse_composite)
+        comp = (type(guide).noise_pred is CompositeGuide.noise_pred and (comp_fused or getattr(guide, 'on_device', False))
                 and hasattr(self.unet, 'forward_nhwc'))
+        comp_fused = comp_fused and comp
         simple = type(guide).noise_pred is SimpleGuide.noise_pred
         device_guide = simple or comp
         # WindowedGuide: a canvas of any size on the UNet's own window size.  The window batch is the loop's persistent buffer,
@@ -441,7 +458,8 @@ class FlexPipeline():
         if sde and step_noise is None:
             step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
         # eta > 0 stays fused for SimpleGuide when the noise comes from the counter-based stream (fd_cfg_ddim_noise_step_f32)
-        noisy = bool(eta) and step_noise is not None and simple
+        # (and for a CompositeGuide: fd_composite_ddim_step_f32)
+        noisy = bool(eta) and step_noise is not None and (simple or comp_fused)
         # the windowed device loop: DDIM (its eta > 0 term from the stream, win_noisy) or the multistep solver (win_ms)
         win_ms = win and isinstance(self.scheduler, DPMSolverMultistepScheduler)
         win_noisy = win and bool(eta) and step_noise is not None and isinstance(self.scheduler, DDIMScheduler)
@@ -451,7 +469,8 @@ class FlexPipeline():
                  and hasattr(self.unet, 'forward_nhwc'))
         # SimpleGuide + DPM-Solver++: the same loop, its step (CFG, x0, history, multistep update, known-region blend) one
         # fd_cfg_multistep_step_f32 launch (the SDE form: fd_cfg_multistep_noise_step_f32); `eta` does not apply to it
-        fused_ms = (simple and isinstance(self.scheduler, DPMSolverMultistepScheduler)
+        # (a CompositeGuide: fd_composite_multistep_step_f32, the entity blend ahead of the CFG combine)
+        fused_ms = ((simple or comp_fused) and isinstance(self.scheduler, DPMSolverMultistepScheduler)
                     and hasattr(self.unet, 'forward_nhwc'))
         # generic and planned routes: a scheduler that takes it draws from the stream at (noise, t_start + i)
         takes_noise = step_noise is not None and 'step_noise' in inspect.signature(self.scheduler.step).parameters
@@ -463,7 +482,8 @@ class FlexPipeline():
         is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
         # SimpleGuide + PLMS / K-LMS on that route: the step (CFG, history write, linear multistep update, known-region blend,
         # K-LMS's next scaled input) is one fd_cfg_linear_multistep_step_f32 launch through `scheduler.fused_step`
-        fused_lin = (planned and simple and not rescale and self.fuse_linear_multistep
+        # (a CompositeGuide: fd_composite_linear_multistep_step_f32)
+        fused_lin = (planned and (simple or comp_fused) and not rescale and self.fuse_linear_multistep
                      and isinstance(self.scheduler, (PNDMScheduler, LMSDiscreteScheduler)))
         planned = planned and not fused_lin
         # WindowedGuide with any scheduler the windowed loop does not step itself: the same route over the window batch
@@ -494,6 +514,9 @@ class FlexPipeline():
         cfg = guide.classifier_free_guidance if device_guide else None
         rep = guide.rep if comp or win else 2 if cfg else 1
         vpred = (fused or win_fused) and self.scheduler.config['prediction_type'] == 'v_prediction'
+        # the composite's weight maps [n][HW] as the schedulers' fused steps take them, built once per latent size (a SimpleGuide:
+        # no keyword, today's call argument for argument)
+        ent = {'entities': guide.entity_rows(H, W)} if comp_fused else {}
         if win_fused or win_planned:
             # the window batch: the one persistent buffer (what the graph / plan reads); the canvas does not evict it
             grid = guide.bind(H, W)
@@ -537,6 +560,11 @@ class FlexPipeline():
                         ops.cfg_rescale_ddim_step(latents, eps, B, C, H * W, guide.guidance, rescale, coef, vpred, mask=blend,
                                                   sigma=float(sigma) if noisy else 0.0, noise=step_noise if noisy else None,
                                                   draw=t_start + i)
+                    elif comp_fused and (noisy or known is not None):
+                        # entity blend + CFG + DDIM update + sigma z + the known-region blend of a masked request in one launch
+                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
+                        guide.step(latents, eps, coef, vpred, mask=blend, sigma=float(sigma) if noisy else 0.0,
+                                   step_noise=(step_noise, t_start + i) if noisy else None)
                     elif noisy:
                         # CFG + DDIM update + sigma z (+ the known-region blend of a masked request) in one launch
                         blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
@@ -554,7 +582,9 @@ class FlexPipeline():
                         ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
                 elif fused_ms:
                     if debug:
-                        eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(), rep=rep)
+                        # (a composite reads the request's time-bias table, as on the DDIM loop; a SimpleGuide: the call as it was)
+                        temb = {'temb': self._temb_row(int(t)).expand(B * rep, -1).contiguous()} if comp and self._temb_tab else {}
+                        eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(), rep=rep, **temb)
                         latents = latents.clone()
                     else:
                         eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
@@ -563,6 +593,10 @@ class FlexPipeline():
                     if rescale:
                         self.scheduler.fused_rescale_step(latents, eps, int(t), B, C, H * W, guide.guidance, rescale, blend,
                                                           (step_noise, t_start + i) if sde else None)
+                    elif comp:
+                        # the entity blend ahead of the CFG combine, in the step's launch
+                        self.scheduler.fused_composite_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, ent['entities'],
+                                                            blend, (step_noise, t_start + i) if sde else None)
                     elif sde:
                         self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend,
                                                   (step_noise, t_start + i))
@@ -577,10 +611,10 @@ class FlexPipeline():
                         last = t_start + i + 1 >= len(self.scheduler.timesteps)
                         self.scheduler.fused_step(latents, eps, t_start + i, B, C, H * W, cfg, guide.guidance, blend,
                                                   scaled_out=None if last else lin_input,
-                                                  next_scale=0.0 if last else lin_scale(t_start + i + 1))
+                                                  next_scale=0.0 if last else lin_scale(t_start + i + 1), **ent)
                     else:
                         eps = self._unet_eps(latents, float(t), guide.stacked_embeds(), rep)
-                        self.scheduler.fused_step(latents, eps, t, B, C, H * W, cfg, guide.guidance, blend)
+                        self.scheduler.fused_step(latents, eps, t, B, C, H * W, cfg, guide.guidance, blend, **ent)
                 elif win_fused:
                     if debug:
                         temb = self._temb_row(int(t)).expand(wins.shape[0] * rep, -1).contiguous() if self._temb_tab else None

@@ -184,6 +184,15 @@ class DDIMScheduler(_Configured):
                          float(np.sqrt(a)), float(np.sqrt(np.float32(1.0) - a)))
 
 
+def _linear_multistep_launch(entities: Optional[torch.Tensor], latents: torch.Tensor, eps_nhwc: torch.Tensor, *args, **kw):
+    '''The one launch of PLMS's and K-LMS's `fused_step`: today's wrapper with today's arguments, or -- `entities` given: the
+    device weight maps fp32 [n][HW] of a CompositeGuide, n == 0 an empty marker -- its composite front over rep-major rows.'''
+    if entities is None:
+        ops.cfg_linear_multistep_step(latents, eps_nhwc, *args, **kw)
+    else:
+        ops.composite_linear_multistep_step(latents, eps_nhwc, entities, *args, **kw)
+
+
 class PNDMScheduler(_Configured):
     '''PLMS branch (skip_prk_steps=True, what Stable Diffusion v1 ships and what the reference's
     `Runner` actually passes, utils.py:70) of diffusers 0.3.0's `PNDMScheduler`, restated
@@ -275,10 +284,12 @@ class PNDMScheduler(_Configured):
         return h
 
     def fused_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
-                   cfg: bool, guidance: float, mask=None):
+                   cfg: bool, guidance: float, mask=None, entities: Optional[torch.Tensor] = None):
         '''`step` as one launch, in place on `latents` (NCHW fp32 [B][C][HW]) from the UNet's NHWC fp32 output: CFG, the guided
         eps into the ring, the multistep combination, the update; mask = (z0, noise, mask [HW], k1, k2) adds the known-region
-        blend.  Returns the ring slots (written or None, [read, newest first]).'''
+        blend.  `entities`: a CompositeGuide's device weight maps fp32 [n][HW] (n == 0: an empty marker) -- eps_nhwc then holds
+        its (cfg + 1 + n) B HW rep-major rows and the launch is fd_composite_linear_multistep_step_f32, the entity blend ahead of
+        the CFG combine.  Returns the ring slots (written or None, [read, newest first]).'''
         if self.ets or self.cur_sample is not None:
             raise RuntimeError('PNDMScheduler: this request already ran `step`; call set_timesteps before `fused_step`')
         t = int(timestep)
@@ -301,8 +312,8 @@ class PNDMScheduler(_Configured):
         slot = n % 4 if write else None
         assert slot not in reads
         cs, ce = self.prev_coefficients(t, prev)
-        ops.cfg_linear_multistep_step(latents, eps_nhwc, 0, [ring[r] for r in reads], None if slot is None else ring[slot], B, C,
-                                      HW, cfg, guidance, weights, (float(cs), float(ce)), mask, x_keep_out=keep, x_src=src)
+        _linear_multistep_launch(entities, latents, eps_nhwc, 0, [ring[r] for r in reads], None if slot is None else ring[slot], B,
+                                 C, HW, cfg, guidance, weights, (float(cs), float(ce)), mask, x_keep_out=keep, x_src=src)
         self._stored = stored
         self.counter += 1
         return slot, reads
@@ -394,12 +405,13 @@ class LMSDiscreteScheduler(_Configured):
 
     def fused_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
                    cfg: bool, guidance: float, mask=None, scaled_out: Optional[torch.Tensor] = None, next_scale: float = 0.0,
-                   order: int = 4):
+                   order: int = 4, entities: Optional[torch.Tensor] = None):
         '''`step` as one fd_cfg_linear_multistep_step_f32 launch, in place on the UNSCALED `latents` (NCHW fp32 [B][C][HW]) from
         the UNet's NHWC fp32 output: CFG, x0, the derivative into the ring (entry n in slot n % 4), the update over the stored
         derivatives with `lms_coefficient(min(i + 1, order), i, k)`; mask = (z0, noise, mask [HW], k1, k2) adds the known-region
         blend; `scaled_out` receives next_scale x', the next step's model input (ops.axpby(x', None, next_scale, 0.0)).
-        `timestep` is the index into `sigmas`, as for `step`.  Returns the ring slots (written, [read, newest first]).'''
+        `timestep` is the index into `sigmas`, as for `step`.  `entities`: as `PNDMScheduler.fused_step`.  Returns the ring
+        slots (written, [read, newest first]).'''
         if self.derivatives:
             raise RuntimeError('LMSDiscreteScheduler: this request already ran `step`; call set_timesteps before `fused_step`')
         if not 1 <= order <= 4:
@@ -414,9 +426,9 @@ class LMSDiscreteScheduler(_Configured):
         coeffs = [self.lms_coefficient(order, i, k) for k in range(min(order, held))]
         slot, reads = n % 4, [(n - k) % 4 for k in range(1, len(coeffs))]
         assert slot not in reads
-        ops.cfg_linear_multistep_step(latents, eps_nhwc, 1, [ring[r] for r in reads], ring[slot], B, C, HW, cfg, guidance,
-                                      [float(c) for c in coeffs], (-sigma, 1.0 / sigma, -1.0 / sigma), mask,
-                                      x_scaled_out=scaled_out, scale=next_scale)
+        _linear_multistep_launch(entities, latents, eps_nhwc, 1, [ring[r] for r in reads], ring[slot], B, C, HW, cfg, guidance,
+                                 [float(c) for c in coeffs], (-sigma, 1.0 / sigma, -1.0 / sigma), mask,
+                                 x_scaled_out=scaled_out, scale=next_scale)
         self._stored = n + 1
         return slot, reads
 
@@ -560,6 +572,21 @@ class DPMSolverMultistepScheduler(_Configured):
         order = self.step_order(i)
         ops.cfg_multistep_step(latents, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C, HW,
                                cfg, guidance, self.step_coefficients(i, order), mask)
+        self._last = i
+
+    def fused_composite_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int, cfg: bool,
+                             guidance: float, entities: torch.Tensor, mask=None, step_noise=None):
+        '''`fused_step` for a CompositeGuide (fd_composite_multistep_step_f32): `entities` are its device weight maps fp32
+        [n][HW] (n == 0: an empty marker), eps_nhwc holds its (cfg + 1 + n) B HW rep-major rows, and the entity blend precedes
+        the CFG combine in the same one launch.  (B, C, HW) must be the real latent: the step noise runs at C HW elements per
+        sample.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).  A method of its own: `fused_step`'s signature is
+        pinned; the step index, the order rule, the history and the coefficients are `fused_step`'s.'''
+        i = self.step_index(timestep)
+        hist = self._history(latents)
+        order = self.step_order(i)
+        co = self.step_coefficients(i, order)
+        ops.composite_multistep_step(latents, eps_nhwc, entities, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C,
+                                     HW, cfg, guidance, co[:5], mask, **self._rescale_noise(i, co, step_noise))
         self._last = i
 
     def _rescale_noise(self, i: int, co, step_noise) -> dict:

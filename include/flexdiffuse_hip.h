@@ -611,6 +611,40 @@ int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0
                                       float guidance, float rescale, float p, float q, float a, float w0, float w1,
                                       float k1, float k2, float sn, uint64_t seed, int64_t sample_offset, int draw,
                                       void* stream);
+/* Region composition under every scheduler, one launch per step (additive; FD_ABI_VERSION stays 12): the steps of
+ * fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32 and fd_cfg_linear_multistep_step_f32 with the entity blend of
+ * fd_composite_step_f32 as the source of the guided e -- the same kernel (k_latent_step, csrc/step.hip), the arguments of the
+ * sibling plus `weights, n_entities`.  eps_nhwc holds (cfg + 1 + n_entities) * B * HW rows, row stride ld >= C, in
+ * fd_composite_step_f32's rep-major order ([uncond] [background] [entity 0] ...: block r, sample b, pixel p -> row
+ * (r * B + b) * HW + p); weights: fp32 [n_entities][HW], shared by the B samples.  With first = cfg ? 1 : 0 and
+ * blk = B * HW * ld, element (b, c, p), row = (b * HW + p) * ld + c, every operation a separately rounded fp32 one:
+ *   v = eps[first * blk + row]
+ *   for k = 0 .. n_entities - 1, ascending:  w = weights[k * HW + p] ;  w != 0:  v = v + w (eps[(first + 1 + k) * blk + row] - v)
+ *   e = cfg ? u + g (v - u), u = eps[row] : v
+ * (no exact branch for w == 1: the lerp is the contract, as in fd_composite_step_f32), then everything the sibling does with
+ * its e.  n_entities == 0 (weights ignored): the sibling's kernel and bits.  float4 accesses need HW % 4 == 0 and 16-byte
+ * bases, weights included; otherwise the scalar kernel runs.  FD_EINVAL before any launch: the sibling's cases, n_entities < 0,
+ * weights NULL with n_entities > 0.
+ * fd_composite_ddim_step_f32: DDIM; eps_out (optional, NCHW fp32) receives e; mask != NULL: the known-region blend (z0, noise,
+ * k1, k2 as fd_cfg_ddim_masked_step_f32); sigma != 0: x' += sigma z from the stream at (seed, sample_offset, per, draw), which
+ * are checked only then.  sigma == 0 and mask == NULL: the bits of fd_composite_step_f32 with do_step. */
+int fd_composite_ddim_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities, float* eps_out,
+                               const float* z0, const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
+                               float guidance, float c1, float c2, float c3, float c4, int v_prediction, float k1, float k2,
+                               float sigma, uint64_t seed, int64_t sample_offset, int per, int draw, void* stream);
+/* DPM-Solver++ (2M), orders 1 (m1 == NULL) and 2; sn == 0 is the ODE form (per and draw are checked as the sibling checks them). */
+int fd_composite_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities, float* m0_out,
+                                    const float* m1, const float* z0, const float* noise, const float* mask, int B, int C,
+                                    int HW, int ld, int cfg, float guidance, float p, float q, float a, float w0, float w1,
+                                    float k1, float k2, float sn, uint64_t seed, int64_t sample_offset, int per, int draw,
+                                    void* stream);
+/* PLMS (form 0) and K-LMS (form 1), n_prev 0..3, every row and rule of fd_cfg_linear_multistep_step_f32. */
+int fd_composite_linear_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities, int form,
+                                           int n_prev, const float* h1, const float* h2, const float* h3, float* h_out,
+                                           float* x_keep_out, const float* x_src, float* x_scaled_out, const float* z0,
+                                           const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
+                                           float guidance, float w0, float w1, float w2, float w3, float a0, float a1, float a2,
+                                           float scale, float k1, float k2, void* stream);
 /* Context schedules (additive; FD_ABI_VERSION stays 12): out[i] = half_rn(a[i] + w * (b[i] - a[i])) on contiguous fp16 buffers of n
  * elements -- the subtraction, the product and the sum three separately rounded fp32 operations (no FMA), one rounding to half.
  * w == 0 stores a's bits, w == 1 stores b's bits; a[i] == b[i] gives a[i] for every w (a zero of either sign: +0 unless w is 0 or 1).
