@@ -14,60 +14,24 @@ its ~310 C-ABI launches recorded once per (shape, context) and re-issued each st
 library call -- the same eager launches in the same order, without the Python front's per-op
 work.  Same kernels, same order, bit-identical results in all three modes.
 
-DPM-Solver++ (`DPMSolverMultistepScheduler`, beyond the reference's pinned diffusers): SimpleGuide runs the same device
-loop with fd_cfg_multistep_step_f32 as its one launch after the UNet (CFG, x0, history write, second-order multistep
-update, and the known-region blend of a masked request).
-
-PLMS and K-LMS (`PNDMScheduler` -- what the reference's Runner passes, utils.py:70 -- and `LMSDiscreteScheduler`): SimpleGuide
-with the graph or the plan on runs the device loop with fd_cfg_linear_multistep_step_f32 as its one launch after the UNet
-(`fused_lin`: CFG, the history write, the linear multistep update, the known-region blend of a masked request; under K-LMS the
-launch also writes the next step's sigma-scaled model input into the persistent buffer, the unscaled latents being a tensor of
-the call's own).  `fuse_linear_multistep = False`, guidance rescale, `debug=True` or a WindowedGuide keep
-the planned route below; with neither graph nor plan the reference protocol runs.  The same bits on all of them.
-
-Composition under every scheduler (`fuse_composite`, default True): every CompositeGuide whose `noise_pred` is the class's own --
-batch 1 with plain rectangles included -- runs on these loops with the entity blend as the source of the guided prediction inside
-the step's one launch: fd_composite_ddim_step_f32 (DDIM with a mask image, or eta > 0 on `pipe.step_noise`),
-fd_composite_multistep_step_f32 (DPM-Solver++ and its SDE form, `scheduler.fused_composite_step`),
-fd_composite_linear_multistep_step_f32 (PLMS and K-LMS, `scheduler.fused_step(entities=)`).  False restores the earlier routes:
-the device loop for a batched or masked composite under DDIM at eta = 0 only (+ a blend-only launch with a mask image), the
-planned route under every other scheduler, `guide.noise_pred` for batch 1.  The route table is DESIGN.md sec. 7.4.
-
-Masked img2img (`mask_image=`, beyond the reference; pipeline/inpaint.py): after every step the kept
-region of the latents is put back on the re-noised init latents -- inside the fused step's own launch
-(fd_cfg_ddim_masked_step_f32) on the SimpleGuide + DDIM loop, by one blend-only launch after the step
-everywhere else.  Without a mask no path changes.
-
-Context schedules (beyond the reference; ctx_schedule.py): a guide with `at_step` (ScheduledGuide, a CompositeGuide with
-`style_linear=`) is told the global step index `t_start + i` at the top of every iteration, on every route, and makes the
-UNet's cached cross-attention projections those of the step's blend of its keyframe contexts -- one fd_lerp_f16 on the
-loop's stream before the graph / plan replay.  Guides without it run unchanged.
-
-Stochastic sampling (`pipe.step_noise`, a `noise.PhiloxNoise`; beyond the reference, which forwards `eta` to its scheduler,
-pipeline/flex.py:247-251): with it, SimpleGuide + DDIM + `eta > 0` stays on the device loop -- one fd_cfg_ddim_noise_step_f32 per
-step, the noise a counter-based stream generated inside the kernel -- and `DPMSolverMultistepSDEScheduler` runs the multistep
-loop with fd_cfg_multistep_noise_step_f32; every other route hands the stream's address to `scheduler.step(step_noise=)`.  The
-result depends on (seed, global sample index, step) only: not on the loop mode, the batch split or the rank count.  Without
-`step_noise`, `eta > 0` is the generator route as before.
-
-Guidance rescale (`guide.guidance_rescale`, beyond the reference; Lin et al. 2023 sec. 3.4): the guided output of each sample is
-scaled by a factor from two of its standard deviations, inside the step's own launch (fd_cfg_rescale_ddim_step_f32,
-fd_cfg_rescale_multistep_step_f32) on the fused loops and by the combine-only form of the first on the planned and generic
-routes -- the same bits on every route.  With 0 every route makes the calls it made before.
-
-Windowed sampling (`WindowedGuide`, beyond the reference; MultiDiffusion, Bar-Tal et al. 2023; windows.py): a canvas larger than
-the model's size is covered by overlapping windows, the UNet runs on all of them as one batch -- the loop's persistent buffer,
-through the graph / plan -- and ONE launch per step combines, averages, takes the step on the canvas and writes the next window
-batch: fd_window_step_f32 (DDIM, eta = 0), fd_window_ddim_step_f32 (a masked request's known-region blend and, with
-`pipe.step_noise`, DDIM's eta > 0 term in that launch), fd_window_multistep_step_f32 (DPM-Solver++ and its SDE form, masked or
-not).  The step noise is addressed by the canvas element (draw = t_start + i), never by the window grid.  PNDM, K-LMS and DDIM
-with eta > 0 on generator noise take a planned route: one fd_window_gather_f32 into the persistent window batch, the graph /
-plan replay, the combine-only form, `scheduler.step`, the blend-only launch of a masked request -- the bits of the loop over
-`guide.noise_pred`, which remains the route of `debug=True` and of a pipeline with neither graph nor plan.
-
-fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32 and fd_cfg_multistep_step_f32 (and their two noise forms) are one kernel (csrc/step.hip) over one
-statement of the step arithmetic (csrc/latent_step.h), which fd_composite_step_f32 calls too: the paths above are bit-equal
-wherever they compute the same thing.
+Which loop a request runs -- and which launch its step ends in -- is decided once per request by `route.select_route`; the table
+of every route is that module's docstring.  `__call__` is: argument checks, the first latents (`_init_latents`), the route, the
+request's state (`_begin`), and a loop that calls ONE step method per iteration (`_step_ddim`, `_step_multistep`, `_step_linear`,
+`_step_window`, `_step_generic`).  Beyond the reference, each on every route and with the same bits on all of them:
+  - DPM-Solver++ and its SDE form, PLMS and K-LMS on the device loop (`fuse_linear_multistep`), the step one launch after the UNet;
+  - composition under every scheduler (`fuse_composite`): the entity blend inside the step's one launch;
+  - masked img2img (`mask_image=`; pipeline/inpaint.py): after every step the kept region of the latents is put back on the
+    re-noised init latents, inside the step's own launch on the device loops, by one blend-only launch after the step elsewhere;
+  - context schedules (ctx_schedule.py): a guide with `at_step` is told the global step index `t_start + i` at the top of every
+    iteration and makes the UNet's cached cross-attention projections those of the step's blend, before the replay reads them;
+  - stochastic sampling (`pipe.step_noise`, a `noise.PhiloxNoise`): the noise is a counter-based stream generated inside the
+    step's launch, or handed to `scheduler.step(step_noise=)`; the result depends on (seed, global sample index, step) only.
+    Without it `eta > 0` is the generator route, as the reference forwards `eta` to its scheduler (pipeline/flex.py:247-251);
+  - guidance rescale (`guide.guidance_rescale`; Lin et al. 2023 sec. 3.4) inside the step's launch or the combine-only launch;
+  - windowed sampling (`WindowedGuide`; MultiDiffusion, windows.py): the window batch is the loop's persistent buffer and ONE
+    launch per step combines, averages, steps the canvas and writes the next window batch.
+The step launches of the simple guide are one kernel (csrc/step.hip) over one statement of the step arithmetic
+(csrc/latent_step.h), which the composite's launches call too: the routes are bit-equal wherever they compute the same thing.
 
 Deliberate differences: E6 initial noise is drawn on the generator's own
 device -- pass a CPU generator for results independent of the GPU count; E8 `init_image`
@@ -77,7 +41,6 @@ from __future__ import annotations
 
 import contextlib
 import gc
-import inspect
 import warnings
 from typing import List, Optional, Tuple, Union
 
@@ -87,10 +50,10 @@ import torch
 from .. import hip, ops
 from ..encode.clip import preprocess
 from ..noise import PhiloxNoise
-from ..scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler,
-                         PNDMScheduler)
-from .guide import GuideBase, SimpleGuide, WindowedGuide, check_guidance_rescale
+from ..scheduler import LMSDiscreteScheduler
+from .guide import GuideBase, check_guidance_rescale
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
+from .route import Route, select_route
 
 VAE_SCALE = 0.18215
 
@@ -118,6 +81,33 @@ class StableDiffusionPipelineOutput():
         if key in ('nsfw_content_detected', 1):
             return self.nsfw_content_detected
         raise KeyError(key)
+
+
+class Known():
+    '''The kept region of a masked img2img request: the clean init latents, the call's noise, the latent mask and the per-step
+    (k1, k2) of `inpaint.known_coefficients`.'''
+    def __init__(self, z0, noise, mask, coef):
+        self.z0, self.noise, self.mask, self.coef = z0, noise, mask, coef
+
+    def at(self, i):
+        '''(z0, noise, mask, k1, k2) of step i, as the step wrappers take their `mask`.'''
+        return (self.z0, self.noise, self.mask, self.coef[i][0], self.coef[i][1])
+
+
+class _Request():
+    '''What the step methods read, fixed before the loop (`FlexPipeline._begin`).'''
+    def __init__(self, route: Route, guide, shape, t_start: int, known: Optional[Known], eta: float, step_noise, debug: bool):
+        self.route, self.guide, self.t_start, self.known = route, guide, t_start, known
+        (self.B, self.C, self.H, self.W), self.eta, self.step_noise, self.debug = shape, eta, step_noise, debug
+        self.step_kwargs = {'eta': eta} if route.accepts_eta else {}     # of `scheduler.step` (+ the step's step_noise)
+        # the CFG switch of a simple or composite guide, the UNet's batch replication, DDIM's prediction type
+        self.cfg, self.rep, self.vpred = None, 1, False
+        self.ent = {}                              # {'entities': the composite's weight maps [n][HW]} when they ride in the step
+        self.grid = self.wins = None               # window loops: the grid and the persistent window batch
+        self.lin_input = None                      # K-LMS on the linear loop: the persistent, sigma-scaled model input
+
+    def mask(self, i: int):
+        return None if self.known is None else self.known.at(i)
 
 
 class FlexPipeline():
@@ -345,6 +335,216 @@ class FlexPipeline():
         return torch.randn(shape, generator=generator, device=gdev,
                            dtype=torch.float32).to(self.device)
 
+    def _init_latents(self, guide, init_image, init_size, strength, generator, latents, noise, mask_image):
+        '''The request's first latents: txt2img noise (or `latents`), or the init image's latents noised to the start level
+        (pipeline/flex.py:186-238).  -> (latents, t_start, the `Known` of a masked request or None).'''
+        batch_size = guide.batch_size
+        if init_image is None:
+            height, width = init_size
+            shape = (batch_size, self.unet.in_channels, height // 8, width // 8)
+            init_latents = self._randn(shape, generator) if latents is None else latents.to(self.device, torch.float32).clone()
+            self.scheduler.set_timesteps(guide.steps)
+            if isinstance(self.scheduler, LMSDiscreteScheduler):   # pipeline/flex.py:236-238
+                init_latents = ops.axpby(init_latents, None, float(self.scheduler.sigmas[0]), 0.0)
+            return init_latents, 0, None
+        if mask_image is not None:
+            mask_hw = image_size(init_image)
+        if not isinstance(init_image, torch.Tensor):
+            init_image = preprocess(init_image)
+        init_image = init_image.to(self.device)
+        init_latents = self.vae.encode(init_image).latent_dist.sample(generator=generator)
+        init_latents = ops.axpby(init_latents, None, VAE_SCALE, 0.0)
+        init_latents = torch.cat([init_latents] * batch_size)
+        offset = self.scheduler.config.get('steps_offset', 0)
+        init_timestep = min(int(guide.steps * strength) + offset, guide.steps)
+        if isinstance(self.scheduler, LMSDiscreteScheduler):
+            t_noise = guide.steps - init_timestep     # pipeline/flex.py:200-204: an index
+        else:
+            t_noise = int(self.scheduler.timesteps[-init_timestep])
+        # one level per sample, as a long tensor (pipeline/flex.py:201-209); built on the host
+        t_noise = torch.tensor([t_noise] * batch_size, dtype=torch.long)
+        noise = self._randn(init_latents.shape, generator) if noise is None else noise.to(self.device, torch.float32)
+        if tuple(noise.shape) != tuple(init_latents.shape):
+            raise ValueError(f'noise {tuple(noise.shape)} does not match the latents {tuple(init_latents.shape)}')
+        t_start = max(guide.steps - init_timestep + offset, 0)
+        known = None
+        if mask_image is not None:
+            # z0 and n stay alive for the loop; add_noise returns a new tensor, so neither aliases the latents
+            z0 = init_latents.to(torch.float32).contiguous()
+            h, w = z0.shape[-2:]
+            if mask_hw[0] % h or mask_hw[1] % w or mask_hw[0] // h != mask_hw[1] // w:
+                raise ValueError(f'init image {mask_hw} is not a whole multiple of its latents {(h, w)}')
+            # uploaded once per call, as z0 and n are
+            mask = latent_mask(mask_image, mask_hw[0], mask_hw[1], mask_hw[0] // h).to(self.device)
+            known = Known(z0, noise.contiguous(), mask, known_coefficients(
+                self.scheduler, self.scheduler.timesteps, t_start, start_level(self.scheduler, int(t_noise[0]))))
+        return self.scheduler.add_noise(init_latents, noise, t_noise), t_start, known
+
+    def _lin_scale(self, j: int) -> float:
+        return 1.0 / ((float(self.scheduler.sigmas[j]) ** 2 + 1) ** 0.5)     # pipeline/flex.py:270-274
+
+    def _begin(self, route: Route, guide, latents, t_start, known, eta, step_noise, debug):
+        '''The request's state and the tensor its loop steps: the persistent buffers a route reads through the graph / plan, the
+        time-embedding table, the composite's weight maps, the window batch.  -> (_Request, latents).'''
+        B, C, H, W = latents.shape
+        s = _Request(route, guide, (B, C, H, W), t_start, known, eta, step_noise, debug)
+        if route.persistent:
+            # persistent latent buffer: the captured UNet graph / recorded plan reads this address (PLMS steps it in place)
+            latents = self.loop_latents(latents)
+        elif route.loop == 'linear':
+            # K-LMS: the persistent buffer holds the SCALED model input (what the graph / plan reads), written by every step's
+            # launch for the next one and by one axpby for the first; the unscaled latents are a tensor of this call's own
+            latents = latents.to(self.device, torch.float32).clone()
+            s.lin_input = self.loop_latents(ops.axpby(latents, None, self._lin_scale(t_start), 0.0))
+        self._temb_tab = None
+        if route.temb_table:
+            # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
+            # instead of three GEMMs per step
+            keys = {}
+            for t in self.scheduler.timesteps[t_start:]:
+                keys.setdefault(float(t), len(keys))
+            self._temb_tab = (keys, self.unet.time_bias_table(list(keys)))
+        # loop-invariant: the CFG switch and the UNet's batch replication of a device guide, DDIM's prediction type
+        if route.guide in ('simple', 'composite'):
+            s.cfg = guide.classifier_free_guidance
+        s.rep = guide.rep if route.guide in ('composite', 'window') else 2 if s.cfg else 1
+        s.vpred = route.loop in ('ddim', 'window') and self.scheduler.config['prediction_type'] == 'v_prediction'
+        if route.fuse_entities:
+            # the composite's weight maps [n][HW] as the schedulers' fused steps take them, built once per latent size
+            s.ent = {'entities': guide.entity_rows(H, W)}
+        if route.loop in ('window', 'window_planned'):
+            # the window batch: the one persistent buffer (what the graph / plan reads); the canvas does not evict it
+            s.grid = guide.bind(H, W)
+            wshape = (B * s.grid.count, C, s.grid.h, s.grid.w)
+            s.wins = self._lat_bufs.get(wshape)
+            if s.wins is None:
+                s.wins = torch.empty(wshape, dtype=torch.float32, device=latents.device)
+                self._lat_bufs = {wshape: s.wins}
+            guide.gather(latents, s.wins)
+        return s, latents
+
+    def _eps(self, s: _Request, x: torch.Tensor, t: int, latents: torch.Tensor):
+        '''The UNet's output on the model input `x` of a fused loop, and the tensor the step writes: the graph / plan replay and
+        `latents` itself, or under `debug` the eager forward and a copy (a composite or windowed guide reads the request's
+        time-bias table as the graph / plan do: bit-equal to them; a SimpleGuide: the call as it was).'''
+        if not s.debug:
+            return self._unet_eps(x, t, s.guide.stacked_embeds(), s.rep), latents
+        table = s.route.guide != 'simple' and self._temb_tab
+        temb = self._temb_row(t).expand(x.shape[0] * s.rep, -1).contiguous() if table else None
+        return self.unet.forward_nhwc(x, t, s.guide.stacked_embeds(), rep=s.rep, temb=temb), latents.clone()
+
+    def _blend_known(self, s: _Request, x: torch.Tensor, i: int):
+        '''Masked img2img behind any scheduler / guide: the blend-only launch on the step's result.'''
+        z0, n, m, k1, k2 = s.known.at(i)
+        ops.cfg_ddim_masked_step(x, None, z0, n, m, s.B, s.C, s.H * s.W, k1=k1, k2=k2)
+
+    def _step_ddim(self, s: _Request, i: int, t, latents):
+        '''DDIM on the device loop: the UNet, then CFG (+ rescale | the entity blend) + the update + sigma z + the known-region
+        blend of a masked request in one launch.'''
+        r, guide, B, C, HW = s.route, s.guide, s.B, s.C, s.H * s.W
+        eps, latents = self._eps(s, latents, int(t), latents)
+        coef = self.scheduler.step_coefficients(int(t), s.eta if r.noisy else 0.0)
+        sigma, coef = float(coef[4]) if r.noisy else 0.0, coef[:4]
+        noise, draw, blend = s.step_noise if r.noisy else None, s.t_start + i, s.mask(i)
+        if r.rescale:
+            ops.cfg_rescale_ddim_step(latents, eps, B, C, HW, guide.guidance, r.rescale, coef, s.vpred, mask=blend, sigma=sigma,
+                                      noise=noise, draw=draw)
+        elif r.fuse_entities and (r.noisy or blend is not None):
+            guide.step(latents, eps, coef, s.vpred, mask=blend, sigma=sigma, step_noise=(noise, draw) if r.noisy else None)
+        elif r.noisy:
+            ops.cfg_ddim_noise_step(latents, eps, B, C, HW, s.cfg, guide.guidance, coef, s.vpred, sigma, noise, C * HW, draw, blend)
+        elif r.guide == 'composite':
+            guide.step(latents, eps, coef, s.vpred)
+            if blend is not None:
+                self._blend_known(s, latents, i)
+        elif blend is not None:
+            ops.cfg_ddim_masked_step(latents, eps, *blend[:3], B, C, HW, s.cfg, guide.guidance, coef, s.vpred, *blend[3:])
+        else:
+            ops.cfg_ddim_step(latents, eps, B, C, HW, s.cfg, guide.guidance, coef, s.vpred)
+        return latents
+
+    def _step_multistep(self, s: _Request, i: int, t, latents):
+        '''DPM-Solver++ and its SDE form on the device loop: the UNet, then the scheduler's one launch (CFG, x0, history,
+        multistep update, step noise, known-region blend), with the rescale or the entity blend ahead of it in that launch.'''
+        r, guide, B, C, HW = s.route, s.guide, s.B, s.C, s.H * s.W
+        eps, latents = self._eps(s, latents, int(t), latents)
+        blend, noise = s.mask(i), (s.step_noise, s.t_start + i) if r.sde else None
+        if r.rescale:
+            self.scheduler.fused_rescale_step(latents, eps, int(t), B, C, HW, guide.guidance, r.rescale, blend, noise)
+        elif r.guide == 'composite':
+            self.scheduler.fused_composite_step(latents, eps, int(t), B, C, HW, s.cfg, guide.guidance, s.ent['entities'], blend, noise)
+        elif r.sde:
+            self.scheduler.fused_step(latents, eps, int(t), B, C, HW, s.cfg, guide.guidance, blend, noise)
+        else:
+            self.scheduler.fused_step(latents, eps, int(t), B, C, HW, s.cfg, guide.guidance, blend)
+        return latents
+
+    def _step_linear(self, s: _Request, i: int, t, latents):
+        '''PLMS and K-LMS on the device loop: the UNet replay, then `scheduler.fused_step` (CFG | the entity blend, the history
+        write, the linear multistep update, the known-region blend) in one launch.'''
+        guide, B, C, HW, j = s.guide, s.B, s.C, s.H * s.W, s.t_start + i
+        if not s.route.is_lms:
+            eps = self._unet_eps(latents, float(t), guide.stacked_embeds(), s.rep)
+            self.scheduler.fused_step(latents, eps, t, B, C, HW, s.cfg, guide.guidance, s.mask(i), **s.ent)
+            return latents
+        # the scheduler steps by sigma index; the UNet sees the float timestep and the scaled buffer, which this step's launch
+        # refills for the next one
+        eps = self._unet_eps(s.lin_input, float(t), guide.stacked_embeds(), s.rep)
+        last = j + 1 >= len(self.scheduler.timesteps)
+        self.scheduler.fused_step(latents, eps, j, B, C, HW, s.cfg, guide.guidance, s.mask(i),
+                                  scaled_out=None if last else s.lin_input, next_scale=0.0 if last else self._lin_scale(j + 1), **s.ent)
+        return latents
+
+    def _step_window(self, s: _Request, i: int, t, latents):
+        '''A windowed canvas on the device loop: the UNet over the window batch, then CFG per window, the average, the update of
+        the canvas, the step noise, the known-region blend and the next window batch (of the blended canvas) in one launch.'''
+        r, guide = s.route, s.guide
+        eps, latents = self._eps(s, s.wins, int(t), latents)
+        if r.multistep:
+            self.scheduler.fused_window_step(latents, s.wins, eps, int(t), s.B, s.C, s.grid.args, guide.blend_code,
+                                             guide.classifier_free_guidance, guide.guidance, s.mask(i),
+                                             (s.step_noise, s.t_start + i) if r.sde else None)
+        else:
+            coef = self.scheduler.step_coefficients(int(t), s.eta if r.noisy else 0.0)
+            guide.step(latents, s.wins, eps, coef[:4], s.vpred, mask=s.mask(i), sigma=float(coef[4]) if r.noisy else 0.0,
+                       step_noise=(s.step_noise, s.t_start + i) if r.noisy else None)
+        return latents
+
+    def _step_generic(self, s: _Request, i: int, t, latents):
+        '''`scheduler.step` on the guided prediction, then the blend-only launch of a masked request.  The prediction: on
+        `planned` and `window_planned` the UNet replay on the persistent buffer and the guide's combine-only launch (the bits of
+        `guide.noise_pred`), else `guide.noise_pred` itself -- the reference protocol (pipeline/flex.py:262-290).'''
+        r, guide, B, C, H, W = s.route, s.guide, s.B, s.C, s.H, s.W
+        t_index, model_input = t, latents
+        if r.is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling
+            t_index = s.t_start + i
+            model_input = ops.axpby(latents, None, self._lin_scale(t_index), 0.0)
+        if r.loop == 'generic':
+            noise_pred = guide.noise_pred(model_input, t)
+        else:
+            noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
+        if r.loop == 'planned':
+            eps = self._unet_eps(self.loop_latents(model_input), float(t), guide.stacked_embeds(), s.rep)
+            if r.guide == 'composite':
+                guide.step(None, eps, eps_out=noise_pred)
+            elif r.rescale:
+                ops.cfg_rescale_ddim_step(None, eps, B, C, H * W, guide.guidance, r.rescale, do_step=False, eps_out=noise_pred)
+            else:
+                ops.cfg_ddim_step(None, eps, B, C, H * W, s.cfg, guide.guidance, do_step=False, eps_out=noise_pred)
+        elif r.loop == 'window_planned':
+            # gather into the persistent window batch, replay, the combine-only form of the windowed step
+            guide.gather(model_input.to(self.device, torch.float32).contiguous(), s.wins)
+            eps = self._unet_eps(s.wins, float(t), guide.stacked_embeds(), s.rep)
+            guide.step(None, None, eps, eps_out=noise_pred)
+        if r.takes_noise:
+            s.step_kwargs['step_noise'] = (s.step_noise, s.t_start + i)
+        latents = self.scheduler.step(noise_pred, t_index, latents, **s.step_kwargs).prev_sample
+        if s.known is not None:
+            # blend the step's own result (not the persistent buffer, which holds the model input)
+            latents = latents.to(self.device, torch.float32).contiguous()
+            self._blend_known(s, latents, i)
+        return latents
+
     @torch.no_grad()
     def __call__(self,
                  guide: GuideBase,
@@ -380,160 +580,23 @@ class FlexPipeline():
         rescale = float(getattr(guide, 'guidance_rescale', 0.0) or 0.0)
         if rescale:
             check_guidance_rescale(rescale, guide.guidance)
-        batch_size = guide.batch_size
         self.scheduler.set_timesteps(guide.steps)
         assert self.scheduler.timesteps is not None
-
-        if init_image is not None:
-            if mask_image is not None:
-                mask_hw = image_size(init_image)
-            if not isinstance(init_image, torch.Tensor):
-                init_image = preprocess(init_image)
-            init_image = init_image.to(self.device)
-            dist = self.vae.encode(init_image).latent_dist
-            init_latents = dist.sample(generator=generator)
-            init_latents = ops.axpby(init_latents, None, VAE_SCALE, 0.0)
-            init_latents = torch.cat([init_latents] * batch_size)
-            offset = self.scheduler.config.get('steps_offset', 0)
-            init_timestep = int(guide.steps * strength) + offset
-            init_timestep = min(init_timestep, guide.steps)
-            if isinstance(self.scheduler, LMSDiscreteScheduler):
-                t_noise = guide.steps - init_timestep     # pipeline/flex.py:200-204: an index
-            else:
-                t_noise = int(self.scheduler.timesteps[-init_timestep])
-            # one level per sample, as a long tensor (pipeline/flex.py:201-209); built on the host
-            t_noise = torch.tensor([t_noise] * batch_size, dtype=torch.long)
-            noise = self._randn(init_latents.shape, generator) if noise is None \
-                else noise.to(self.device, torch.float32)
-            if tuple(noise.shape) != tuple(init_latents.shape):
-                raise ValueError(f'noise {tuple(noise.shape)} does not match the latents {tuple(init_latents.shape)}')
-            if mask_image is not None:
-                # z0 and n stay alive for the loop; add_noise returns a new tensor, so neither aliases the latents
-                mask_z0, mask_n = init_latents.to(torch.float32).contiguous(), noise.contiguous()
-                h, w = mask_z0.shape[-2:]
-                if mask_hw[0] % h or mask_hw[1] % w or mask_hw[0] // h != mask_hw[1] // w:
-                    raise ValueError(f'init image {mask_hw} is not a whole multiple of its latents {(h, w)}')
-                # uploaded once per call, as z0 and n are
-                mask_dev = latent_mask(mask_image, mask_hw[0], mask_hw[1], mask_hw[0] // h).to(self.device)
-                mask_start = start_level(self.scheduler, int(t_noise[0]))
-            init_latents = self.scheduler.add_noise(init_latents, noise, t_noise)
-            t_start = max(guide.steps - init_timestep + offset, 0)
-        else:
-            height, width = init_size
-            channels = self.unet.in_channels
-            shape = (batch_size, channels, height // 8, width // 8)
-            init_latents = self._randn(shape, generator) if latents is None \
-                else latents.to(self.device, torch.float32).clone()
-            self.scheduler.set_timesteps(guide.steps)
-            if isinstance(self.scheduler, LMSDiscreteScheduler):   # pipeline/flex.py:236-238
-                init_latents = ops.axpby(init_latents, None, float(self.scheduler.sigmas[0]), 0.0)
-            t_start = 0
-
-        accepts_eta = 'eta' in set(inspect.signature(self.scheduler.step).parameters.keys())
-        extra_step_kwargs = {'eta': eta} if accepts_eta else {}
-
-        latents = init_latents.contiguous()
-        all_latents = [init_latents] if debug else None
-        from ..composition.guide import CompositeGuide
-        # CompositeGuide: blend + CFG + the scheduler's update in one launch per step after the UNet forward over its E context
-        # blocks (`fuse_composite` off: batched samples or masks only, the batch-1 rectangle path on the generic protocol)
-        comp_fused = bool(self.fuse_composite)
-        comp = (type(guide).noise_pred is CompositeGuide.noise_pred and (comp_fused or getattr(guide, 'on_device', False))
-                and hasattr(self.unet, 'forward_nhwc'))
-        comp_fused = comp_fused and comp
-        simple = type(guide).noise_pred is SimpleGuide.noise_pred
-        device_guide = simple or comp
-        # WindowedGuide: a canvas of any size on the UNet's own window size.  The window batch is the loop's persistent buffer,
-        # the canvas an ordinary tensor.  DDIM (eta = 0, or eta > 0 on the counter-based stream) and DPM-Solver++ (ODE and
-        # SDE): a step is the UNet replay + ONE launch (win_fused, below); every other scheduler: the planned route (gather,
-        # replay, combine-only, scheduler.step), or with debug / without graph and plan the generic branch through
-        # guide.noise_pred
-        win = type(guide).noise_pred is WindowedGuide.noise_pred and hasattr(self.unet, 'forward_nhwc')
-        if win and rescale:
-            raise ValueError('WindowedGuide does not support guidance_rescale')
-        rescale = rescale if simple else 0.0     # any other guide applies (or ignores) its own attribute in its noise_pred
+        route = select_route(guide, self.scheduler, self.unet, eta=eta, step_noise=self.step_noise, rescale=rescale, debug=debug,
+                             use_graph=self.use_graph, use_plan=self.use_plan, fuse_composite=self.fuse_composite,
+                             fuse_linear_multistep=self.fuse_linear_multistep)
+        latents, t_start, known = self._init_latents(guide, init_image, init_size, strength, generator, latents, noise, mask_image)
+        all_latents = [latents] if debug else None
         # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
         step_noise = self.step_noise
-        sde = isinstance(self.scheduler, DPMSolverMultistepSDEScheduler)
-        if sde and step_noise is None:
+        if route.sde and step_noise is None:
             step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
-        # eta > 0 stays fused for SimpleGuide when the noise comes from the counter-based stream (fd_cfg_ddim_noise_step_f32)
-        # (and for a CompositeGuide: fd_composite_ddim_step_f32)
-        noisy = bool(eta) and step_noise is not None and (simple or comp_fused)
-        # the windowed device loop: DDIM (its eta > 0 term from the stream, win_noisy) or the multistep solver (win_ms)
-        win_ms = win and isinstance(self.scheduler, DPMSolverMultistepScheduler)
-        win_noisy = win and bool(eta) and step_noise is not None and isinstance(self.scheduler, DDIMScheduler)
-        win_fused = win_ms or win_noisy or (win and isinstance(self.scheduler, DDIMScheduler) and not eta)
-        fused = (device_guide
-                 and isinstance(self.scheduler, DDIMScheduler) and (not eta or noisy)
-                 and hasattr(self.unet, 'forward_nhwc'))
-        # SimpleGuide + DPM-Solver++: the same loop, its step (CFG, x0, history, multistep update, known-region blend) one
-        # fd_cfg_multistep_step_f32 launch (the SDE form: fd_cfg_multistep_noise_step_f32); `eta` does not apply to it
-        # (a CompositeGuide: fd_composite_multistep_step_f32, the entity blend ahead of the CFG combine)
-        fused_ms = ((simple or comp_fused) and isinstance(self.scheduler, DPMSolverMultistepScheduler)
-                    and hasattr(self.unet, 'forward_nhwc'))
-        # generic and planned routes: a scheduler that takes it draws from the stream at (noise, t_start + i)
-        takes_noise = step_noise is not None and 'step_noise' in inspect.signature(self.scheduler.step).parameters
-        B, C, H, W = latents.shape
-        # SimpleGuide with ANY other scheduler (PNDM -- what the reference's Runner passes, utils.py:70 -- LMS, DDIM with
-        # eta): the UNet forward still comes from the launch plan / graph; only the scheduler arithmetic stays generic
-        planned = (not fused and not fused_ms and device_guide and hasattr(self.unet, 'forward_nhwc')
-                   and (self.use_graph or self.use_plan) and not debug)
-        is_lms = isinstance(self.scheduler, LMSDiscreteScheduler)
-        # SimpleGuide + PLMS / K-LMS on that route: the step (CFG, history write, linear multistep update, known-region blend,
-        # K-LMS's next scaled input) is one fd_cfg_linear_multistep_step_f32 launch through `scheduler.fused_step`
-        # (a CompositeGuide: fd_composite_linear_multistep_step_f32)
-        fused_lin = (planned and (simple or comp_fused) and not rescale and self.fuse_linear_multistep
-                     and isinstance(self.scheduler, (PNDMScheduler, LMSDiscreteScheduler)))
-        planned = planned and not fused_lin
-        # WindowedGuide with any scheduler the windowed loop does not step itself: the same route over the window batch
-        win_planned = win and not win_fused and (self.use_graph or self.use_plan) and not debug
-        if (fused or fused_ms) and (self.use_graph or self.use_plan) and not debug:
-            # persistent latent buffer: the captured UNet graph / recorded plan reads this address
-            latents = self.loop_latents(latents)
-        lin_scale = lambda j: 1.0 / ((float(self.scheduler.sigmas[j]) ** 2 + 1) ** 0.5)   # noqa: E731 -- pipeline/flex.py:270-274
-        if fused_lin and is_lms:
-            # K-LMS: the persistent buffer holds the SCALED model input (what the graph / plan reads), written by every step's
-            # launch for the next one and by one axpby for the first; the unscaled latents are a tensor of this call's own
-            latents = latents.to(self.device, torch.float32).clone()
-            lin_input = self.loop_latents(ops.axpby(latents, None, lin_scale(t_start), 0.0))
-        elif fused_lin:
-            # PLMS: the latents live in the persistent buffer and are stepped in place
-            latents = self.loop_latents(latents)
-        known = known_coefficients(self.scheduler, self.scheduler.timesteps, t_start, mask_start) if mask_image is not None else None
-        self._temb_tab = None
-        if (fused or fused_ms or fused_lin or planned or win_fused or win_planned) and hasattr(self.unet, 'time_bias_table'):
-            # the time embedding depends on t only: all of the request's timesteps in one pass (three GEMMs over len(timesteps) rows)
-            # instead of three GEMMs per step
-            ts = [float(t) for t in self.scheduler.timesteps[t_start:]]
-            keys = {}
-            for t in ts:
-                keys.setdefault(t, len(keys))
-            self._temb_tab = (keys, self.unet.time_bias_table(list(keys)))
-        # loop-invariant: the CFG switch and the UNet's batch replication of a device guide, DDIM's prediction type
-        cfg = guide.classifier_free_guidance if device_guide else None
-        rep = guide.rep if comp or win else 2 if cfg else 1
-        vpred = (fused or win_fused) and self.scheduler.config['prediction_type'] == 'v_prediction'
-        # the composite's weight maps [n][HW] as the schedulers' fused steps take them, built once per latent size (a SimpleGuide:
-        # no keyword, today's call argument for argument)
-        ent = {'entities': guide.entity_rows(H, W)} if comp_fused else {}
-        if win_fused or win_planned:
-            # the window batch: the one persistent buffer (what the graph / plan reads); the canvas does not evict it
-            grid = guide.bind(H, W)
-            wshape = (B * grid.count, C, grid.h, grid.w)
-            wins = self._lat_bufs.get(wshape)
-            if wins is None:
-                wins = torch.empty(wshape, dtype=torch.float32, device=latents.device)
-                self._lat_bufs = {wshape: wins}
-            guide.gather(latents, wins)
-
+        s, latents = self._begin(route, guide, latents.contiguous(), t_start, known, eta, step_noise, debug)
+        step = {'ddim': self._step_ddim, 'multistep': self._step_multistep, 'linear': self._step_linear,
+                'window': self._step_window}.get(route.loop, self._step_generic)
         # a guide with a context schedule (ScheduledGuide, CompositeGuide(style_linear=)): told the GLOBAL step index at the top of
         # every iteration, on every route; guides without `at_step` run as before
         at_step = getattr(guide, 'at_step', None)
-
-        def blend_known(x, i):
-            # masked img2img behind any scheduler / guide: the blend-only launch on the step's result
-            ops.cfg_ddim_masked_step(x, None, mask_z0, mask_n, mask_dev, B, C, H * W, k1=known[i][0], k2=known[i][1])
         # The host only has to stay ahead of the device queue.  A generation-2 collection of the
         # cyclic GC walks every tracked object of the process (~175 k with the SD1.5 weights:
         # ~40 ms) and drains that queue, so collections wait until the images are decoded.
@@ -542,130 +605,7 @@ class FlexPipeline():
                 if at_step is not None:
                     # a context schedule: the step's blend, issued eagerly on the loop's stream before the graph / plan replay reads it
                     at_step(t_start + i)
-                if fused:
-                    if debug:
-                        # (a composite reads the request's time-bias table as the graph / plan do: bit-equal to them)
-                        temb = self._temb_row(int(t)).expand(B * rep, -1).contiguous() if comp and self._temb_tab else None
-                        eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(),
-                                                     rep=rep, temb=temb)
-                    else:
-                        eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
-                    coef = self.scheduler.step_coefficients(int(t), eta if noisy else 0.0)
-                    sigma, coef = coef[4], coef[:4]
-                    if debug:
-                        latents = latents.clone()
-                    if rescale:
-                        # CFG + rescale + DDIM update (+ sigma z, + the known-region blend) in one launch
-                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                        ops.cfg_rescale_ddim_step(latents, eps, B, C, H * W, guide.guidance, rescale, coef, vpred, mask=blend,
-                                                  sigma=float(sigma) if noisy else 0.0, noise=step_noise if noisy else None,
-                                                  draw=t_start + i)
-                    elif comp_fused and (noisy or known is not None):
-                        # entity blend + CFG + DDIM update + sigma z + the known-region blend of a masked request in one launch
-                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                        guide.step(latents, eps, coef, vpred, mask=blend, sigma=float(sigma) if noisy else 0.0,
-                                   step_noise=(step_noise, t_start + i) if noisy else None)
-                    elif noisy:
-                        # CFG + DDIM update + sigma z (+ the known-region blend of a masked request) in one launch
-                        blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                        ops.cfg_ddim_noise_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred, float(sigma),
-                                                step_noise, C * H * W, t_start + i, blend)
-                    elif comp:
-                        guide.step(latents, eps, coef, vpred)
-                        if known is not None:
-                            blend_known(latents, i)
-                    elif known is not None:
-                        # CFG + DDIM update + known-region blend in the one launch of the unmasked step
-                        ops.cfg_ddim_masked_step(latents, eps, mask_z0, mask_n, mask_dev, B, C, H * W, cfg,
-                                                 guide.guidance, coef, vpred, known[i][0], known[i][1])
-                    else:
-                        ops.cfg_ddim_step(latents, eps, B, C, H * W, cfg, guide.guidance, coef, vpred)
-                elif fused_ms:
-                    if debug:
-                        # (a composite reads the request's time-bias table, as on the DDIM loop; a SimpleGuide: the call as it was)
-                        temb = {'temb': self._temb_row(int(t)).expand(B * rep, -1).contiguous()} if comp and self._temb_tab else {}
-                        eps = self.unet.forward_nhwc(latents, int(t), guide.stacked_embeds(), rep=rep, **temb)
-                        latents = latents.clone()
-                    else:
-                        eps = self._unet_eps(latents, int(t), guide.stacked_embeds(), rep)
-                    # masked img2img: the blend rides in the step's launch
-                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                    if rescale:
-                        self.scheduler.fused_rescale_step(latents, eps, int(t), B, C, H * W, guide.guidance, rescale, blend,
-                                                          (step_noise, t_start + i) if sde else None)
-                    elif comp:
-                        # the entity blend ahead of the CFG combine, in the step's launch
-                        self.scheduler.fused_composite_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, ent['entities'],
-                                                            blend, (step_noise, t_start + i) if sde else None)
-                    elif sde:
-                        self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend,
-                                                  (step_noise, t_start + i))
-                    else:
-                        self.scheduler.fused_step(latents, eps, int(t), B, C, H * W, cfg, guide.guidance, blend)
-                elif fused_lin:
-                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                    if is_lms:
-                        # the scheduler steps by sigma index; the UNet sees the float timestep and the scaled buffer, which
-                        # this step's launch refills for the next one
-                        eps = self._unet_eps(lin_input, float(t), guide.stacked_embeds(), rep)
-                        last = t_start + i + 1 >= len(self.scheduler.timesteps)
-                        self.scheduler.fused_step(latents, eps, t_start + i, B, C, H * W, cfg, guide.guidance, blend,
-                                                  scaled_out=None if last else lin_input,
-                                                  next_scale=0.0 if last else lin_scale(t_start + i + 1), **ent)
-                    else:
-                        eps = self._unet_eps(latents, float(t), guide.stacked_embeds(), rep)
-                        self.scheduler.fused_step(latents, eps, t, B, C, H * W, cfg, guide.guidance, blend, **ent)
-                elif win_fused:
-                    if debug:
-                        temb = self._temb_row(int(t)).expand(wins.shape[0] * rep, -1).contiguous() if self._temb_tab else None
-                        eps = self.unet.forward_nhwc(wins, int(t), guide.stacked_embeds(), rep=rep, temb=temb)
-                        latents = latents.clone()
-                    else:
-                        eps = self._unet_eps(wins, int(t), guide.stacked_embeds(), rep)
-                    # CFG per window, the average, the update of the canvas, the step noise, the known-region blend of a masked
-                    # request and the next window batch (of the blended canvas) in one launch
-                    blend = None if known is None else (mask_z0, mask_n, mask_dev, known[i][0], known[i][1])
-                    if win_ms:
-                        self.scheduler.fused_window_step(latents, wins, eps, int(t), B, C, grid.args, guide.blend_code,
-                                                         guide.classifier_free_guidance, guide.guidance, blend,
-                                                         (step_noise, t_start + i) if sde else None)
-                    else:
-                        coef = self.scheduler.step_coefficients(int(t), eta if win_noisy else 0.0)
-                        guide.step(latents, wins, eps, coef[:4], vpred, mask=blend, sigma=float(coef[4]) if win_noisy else 0.0,
-                                   step_noise=(step_noise, t_start + i) if win_noisy else None)
-                else:
-                    t_index, model_input = t, latents
-                    if is_lms:        # pipeline/flex.py:270-274: continuous-ODE input scaling
-                        t_index = t_start + i
-                        sigma = float(self.scheduler.sigmas[t_index])
-                        model_input = ops.axpby(latents, None, 1.0 / ((sigma ** 2 + 1) ** 0.5), 0.0)
-                    if planned:
-                        eps = self._unet_eps(self.loop_latents(model_input), float(t), guide.stacked_embeds(), rep)
-                        noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
-                        if comp:
-                            guide.step(None, eps, eps_out=noise_pred)
-                        elif rescale:
-                            ops.cfg_rescale_ddim_step(None, eps, B, C, H * W, guide.guidance, rescale, do_step=False,
-                                                      eps_out=noise_pred)
-                        else:
-                            ops.cfg_ddim_step(None, eps, B, C, H * W, cfg, guide.guidance, do_step=False, eps_out=noise_pred)
-                    elif win_planned:
-                        # guide.noise_pred with the UNet forward from the graph / plan: gather into the persistent window batch,
-                        # replay, the combine-only form of the windowed step
-                        guide.gather(model_input.to(self.device, torch.float32).contiguous(), wins)
-                        eps = self._unet_eps(wins, float(t), guide.stacked_embeds(), rep)
-                        noise_pred = torch.empty((B, C, H, W), dtype=torch.float32, device=latents.device)
-                        guide.step(None, None, eps, eps_out=noise_pred)
-                    else:
-                        noise_pred = guide.noise_pred(model_input, t)
-                    if takes_noise:
-                        extra_step_kwargs['step_noise'] = (step_noise, t_start + i)
-                    latents = self.scheduler.step(noise_pred, t_index, latents,
-                                                  **extra_step_kwargs).prev_sample
-                    if known is not None:
-                        # blend the step's own result (not the persistent buffer, which holds the model input)
-                        latents = latents.to(self.device, torch.float32).contiguous()
-                        blend_known(latents, i)
+                latents = step(s, i, t, latents)
                 if all_latents is not None:
                     all_latents.append(latents)
             # the fused loop ran on the persistent per-shape buffer, which the next call overwrites:

@@ -567,11 +567,16 @@ class DPMSolverMultistepScheduler(_Configured):
                    cfg: bool, guidance: float, mask=None):
         '''One launch, in place on `latents` (NCHW fp32 [B][C][HW]) from the UNet's NHWC fp32 output:
         CFG, x0 into the history, the update; mask = (z0, noise, mask [HW], k1, k2) adds the known-region blend.'''
+        self._fused(latents, timestep, lambda i, m0, m1, co: ops.cfg_multistep_step(
+            latents, eps_nhwc, m0, m1, B, C, HW, cfg, guidance, co, mask))
+
+    def _fused(self, x: torch.Tensor, timestep, launch):
+        '''What every one-launch step on `x` (the latents, or a windowed request's canvas) shares: the step index, the history
+        rows, the order and its coefficients, handed to `launch(i, m0_out, m1, co)`; the history then holds step i.'''
         i = self.step_index(timestep)
-        hist = self._history(latents)
+        hist = self._history(x)
         order = self.step_order(i)
-        ops.cfg_multistep_step(latents, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C, HW,
-                               cfg, guidance, self.step_coefficients(i, order), mask)
+        launch(i, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, self.step_coefficients(i, order))
         self._last = i
 
     def fused_composite_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int, cfg: bool,
@@ -581,13 +586,8 @@ class DPMSolverMultistepScheduler(_Configured):
         the CFG combine in the same one launch.  (B, C, HW) must be the real latent: the step noise runs at C HW elements per
         sample.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).  A method of its own: `fused_step`'s signature is
         pinned; the step index, the order rule, the history and the coefficients are `fused_step`'s.'''
-        i = self.step_index(timestep)
-        hist = self._history(latents)
-        order = self.step_order(i)
-        co = self.step_coefficients(i, order)
-        ops.composite_multistep_step(latents, eps_nhwc, entities, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C,
-                                     HW, cfg, guidance, co[:5], mask, **self._rescale_noise(i, co, step_noise))
-        self._last = i
+        self._fused(latents, timestep, lambda i, m0, m1, co: ops.composite_multistep_step(
+            latents, eps_nhwc, entities, m0, m1, B, C, HW, cfg, guidance, co[:5], mask, **self._rescale_noise(i, co, step_noise)))
 
     def _rescale_noise(self, i: int, co, step_noise) -> dict:
         '''The noise arguments of the rescaled and of the windowed launch: none for the ODE solver.'''
@@ -600,13 +600,9 @@ class DPMSolverMultistepScheduler(_Configured):
         update, the blend of `mask` = (z0, noise, mask [H W], k1, k2) and writes the next window batch into `wins`.  The
         history is canvas-shaped.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).  A method of its own:
         `fused_step`'s signature is pinned.'''
-        i = self.step_index(timestep)
-        hist = self._history(canvas)
-        order = self.step_order(i)
-        co = self.step_coefficients(i, order)
-        ops.window_multistep_step(canvas, wins, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C,
-                                  grid_args, blend, cfg, guidance, co[:5], mask, **self._rescale_noise(i, co, step_noise))
-        self._last = i
+        self._fused(canvas, timestep, lambda i, m0, m1, co: ops.window_multistep_step(
+            canvas, wins, eps_nhwc, m0, m1, B, C, grid_args, blend, cfg, guidance, co[:5], mask,
+            **self._rescale_noise(i, co, step_noise)))
 
     def fused_rescale_step(self, latents: torch.Tensor, eps_nhwc: torch.Tensor, timestep, B: int, C: int, HW: int,
                            guidance: float, rescale: float, mask=None, step_noise=None):
@@ -614,13 +610,8 @@ class DPMSolverMultistepScheduler(_Configured):
         (eps_nhwc holds both halves) and the guided output of each sample is scaled by its factor before x0.  (B, C, HW)
         must be the real latent, the sample the statistics run over.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).
         A method of its own: `fused_step`'s signature is pinned.'''
-        i = self.step_index(timestep)
-        hist = self._history(latents)
-        order = self.step_order(i)
-        co = self.step_coefficients(i, order)
-        ops.cfg_rescale_multistep_step(latents, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C, HW,
-                                       guidance, rescale, co[:5], mask, **self._rescale_noise(i, co, step_noise))
-        self._last = i
+        self._fused(latents, timestep, lambda i, m0, m1, co: ops.cfg_rescale_multistep_step(
+            latents, eps_nhwc, m0, m1, B, C, HW, guidance, rescale, co[:5], mask, **self._rescale_noise(i, co, step_noise)))
 
     def step(self, model_output: torch.Tensor, timestep, sample: torch.Tensor, **_):
         B, C, H, W = sample.shape
@@ -686,14 +677,12 @@ class DPMSolverMultistepSDEScheduler(DPMSolverMultistepScheduler):
         '''The parent's one launch plus sn z.  `step_noise` = (PhiloxNoise, draw), default (PhiloxNoise(0), the step's
         index); `per`: elements per sample, default C * HW (pass it when (B, C) is a view of the real latent).'''
         from .noise import PhiloxNoise
-        i = self.step_index(timestep)
-        hist = self._history(latents)
-        order = self.step_order(i)
-        co = self.step_coefficients(i, order)
-        noise, draw = step_noise if step_noise is not None else (PhiloxNoise(0), i)
-        ops.cfg_multistep_noise_step(latents, eps_nhwc, hist[i & 1], hist[1 - (i & 1)] if order == 2 else None, B, C, HW,
-                                     cfg, guidance, co[:5], co[5], noise, C * HW if per is None else per, int(draw), mask)
-        self._last = i
+
+        def launch(i, m0, m1, co):
+            noise, draw = step_noise if step_noise is not None else (PhiloxNoise(0), i)
+            ops.cfg_multistep_noise_step(latents, eps_nhwc, m0, m1, B, C, HW, cfg, guidance, co[:5], co[5], noise,
+                                         C * HW if per is None else per, int(draw), mask)
+        self._fused(latents, timestep, launch)
 
     def _rescale_noise(self, i: int, co, step_noise) -> dict:
         from .noise import PhiloxNoise

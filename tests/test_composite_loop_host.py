@@ -20,6 +20,7 @@ import torch
 
 import composite_step_ref as cref
 import lin_ref
+from route_trace import _guide, _recording_pipe
 
 B, C, H, W = 2, 4, 3, 5
 HW = H * W
@@ -142,81 +143,6 @@ def test_pipeline_attribute_and_scheduler_signatures():
 
 
 # ---- 3. routes ---------------------------------------------------------------------------------------------------------
-class _Enc():
-    def prompt(self, p):
-        return torch.zeros((1 if isinstance(p, str) else len(p), 4, 8))
-
-
-class _UNet():
-    device = torch.device('cpu')
-    in_channels = 4
-
-    def __init__(self, events):
-        self.events = events
-
-    def forward_nhwc(self, latents, t, ctx, rep=1, temb=None):
-        self.events.append('eager')
-        b, _, h, w = latents.shape
-        assert ctx.shape[0] == rep * b
-        return torch.zeros((rep * b * h * w, 4))
-
-
-class _VAE():
-    def encode(self, image):
-        lat = torch.full((1, 4, image.shape[-2] // 8, image.shape[-1] // 8), 0.25)
-        return type('E', (), {'latent_dist': type('D', (), {'sample': staticmethod(lambda generator=None: lat)})()})()
-
-
-def _recording_pipe(monkeypatch, kind):
-    '''A FlexPipeline on CPU tensors whose library calls are recorded, not made: the UNet replay ('replay'), the eager forward
-    ('eager'), `guide.noise_pred` ('noise_pred'), `scheduler.step` ('scheduler.step', its own launches not listed) and the
-    name of every other hip.call.'''
-    from flexdiffuse_amd import hip
-    from flexdiffuse_amd.pipeline.flex import FlexPipeline
-    events, quiet = [], [0]
-    monkeypatch.setattr(hip, 'call', lambda name, *a: None if quiet[0] else events.append(name))
-    monkeypatch.setattr(hip, 'stream', lambda: None)
-    monkeypatch.setattr(hip, 'require_device', lambda *t: None)
-    sched = _sched(kind)
-    pipe = FlexPipeline(_VAE(), None, None, _UNet(events), sched)
-    pipe._latents_to_image = lambda lat, pil=True: []
-
-    def replay(latents, t, ctx, rep):
-        events.append('replay')
-        b, _, h, w = latents.shape
-        return torch.zeros((rep * b * h * w, 4))
-    pipe._unet_eps = replay
-    step = sched.step
-
-    def quiet_step(*a, **k):
-        events.append('scheduler.step')
-        quiet[0] += 1
-        try:
-            return step(*a, **k)
-        finally:
-            quiet[0] -= 1
-    sched.step = quiet_step
-    return pipe, events
-
-
-def _guide(kind, unet, events):
-    from flexdiffuse_amd.composition import CompositeGuide, EntitySchema, Schema
-    from flexdiffuse_amd.pipeline.guide import SimpleGuide
-    enc = _Enc()
-    if kind == 'simple':
-        g = SimpleGuide(enc, unet, G, 4, enc.prompt(['a', 'b']))
-    else:
-        schema = Schema('bg', '', '', (0.0, 1.0), [EntitySchema('a', (8, 8), (24, 16), 0.8), EntitySchema('b', (16, 0), (32, 32), 0.5)])
-        g = CompositeGuide(enc, unet, G, schema, 4, batch_size=2 if kind == 'comp-batched' else 1)
-        assert g.on_device == (kind == 'comp-batched')
-
-    def noise_pred(latents, step):
-        events.append('noise_pred')
-        return torch.zeros(tuple(latents.shape))
-    g.noise_pred = noise_pred               # the instance's: `type(guide).noise_pred` stays the class's own
-    return g
-
-
 def expected_route(guide, sched, eta, noise, mask, debug, fuse):
     '''The last step's calls by the table of DESIGN.md sec. 7 ("Composition under every scheduler").'''
     blend = ['fd_cfg_ddim_masked_step_f32'] if mask else []
