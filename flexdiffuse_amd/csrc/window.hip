@@ -18,17 +18,9 @@
 // fd_cfg_ddim_step_f32 (the other two fronts: to fd_cfg_ddim_noise_step_f32 / fd_cfg_multistep_[noise_]step_f32).
 #include "latent_step.h"
 #include "philox.h"
+#include "window_grid.h"
 
-enum { FD_WINDOW_MAX = 16, FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
-
-struct FdWindowGrid {
-    int H, W, h, w, sy, sx, ny, nx;
-};
-
-__host__ __device__ __forceinline__ int fd_window_offset(int i, int d, int S, int s) {
-    const int o = i * d;
-    return o < S - s ? o : S - s;
-}
+enum { FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
 
 // One thread owns one element of the window batch: the stores are contiguous, the loads contiguous along a window row.
 __global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ canvas, float* __restrict__ windows,
@@ -154,22 +146,6 @@ __global__ __launch_bounds__(256) void k_window_step(const FdWindowStepArgs a) {
             }
         }
     }
-}
-
-// the checks the two entry points share: the grid's own rule, restated on the host
-static int fd_window_grid_args(const char* who, int B, int C, const FdWindowGrid& g) {
-    FD_CHECK_ARG(B > 0 && C > 0 && g.h > 0 && g.w > 0, FD_EINVAL, "%s: sizes", who);
-    FD_CHECK_ARG(g.h <= g.H && g.w <= g.W, FD_EINVAL, "%s: the window (%d, %d) is larger than the canvas (%d, %d)", who,
-                 g.h, g.w, g.H, g.W);
-    FD_CHECK_ARG(g.sy >= 1 && g.sy <= g.h && g.sx >= 1 && g.sx <= g.w, FD_EINVAL,
-                 "%s: the stride (%d, %d) is outside [1, window]: windows would leave gaps", who, g.sy, g.sx);
-    FD_CHECK_ARG(g.ny >= 1 && g.nx >= 1 && g.ny <= FD_WINDOW_MAX && g.nx <= FD_WINDOW_MAX, FD_EINVAL,
-                 "%s: %d x %d windows: more than %d on an axis", who, g.ny, g.nx, (int)FD_WINDOW_MAX);
-    FD_CHECK_ARG(g.ny == (g.H - g.h + g.sy - 1) / g.sy + 1 && g.nx == (g.W - g.w + g.sx - 1) / g.sx + 1, FD_EINVAL,
-                 "%s: %d x %d windows do not match the count rule ceil((S - s) / d) + 1", who, g.ny, g.nx);
-    FD_CHECK_ARG((unsigned long long)B * g.ny * g.nx * g.h * g.w <= 0x7fffffffull &&
-                     (unsigned long long)g.H * g.W <= 0x7fffffffull, FD_EINVAL, "%s: sizes: cells past 2^31", who);
-    return FD_OK;
 }
 
 extern "C" int fd_window_gather_f32(const float* canvas, float* windows, int B, int C, int H, int W, int h, int w,

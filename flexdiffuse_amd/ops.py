@@ -1328,6 +1328,22 @@ def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, g
     hip.call('fd_window_gather_f32', canvas.data_ptr(), windows.data_ptr(), B, C, *(int(v) for v in grid), hip.stream())
 
 
+def tile_blend(tiles: torch.Tensor, B: int, C: int, grid, feather, a: float = 1.0, b: float = 0.0, clamp01: bool = False,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    '''Tile batch -> canvas (fd_tile_blend_f32): tiles [B Tn * h w][ld] NHWC fp32 rows in fd_window_gather_f32's batch order
+    -> (B, C, H, W) NCHW fp32, per element the feathered average of the covering tiles (weight min(l + 1, E - l, F) per
+    axis, `feather` = (F_y, F_x)), then y = u a + b and the optional clamp to [0, 1].  grid: `windows.WindowGrid.args` in the
+    units of the output.'''
+    H, W, h, w, _, _, ny, nx = grid
+    _check_eps_rows(tiles, B * ny * nx * h * w, C)
+    if out is None:
+        out = _empty((B, C, H, W), torch.float32, tiles)
+    _check_f32(B * C * H * W, out)
+    hip.call('fd_tile_blend_f32', tiles.data_ptr(), out.data_ptr(), B, C, tiles.stride(0), *(int(v) for v in grid),
+             int(feather[0]), int(feather[1]), float(a), float(b), int(clamp01), hip.stream())
+    return out
+
+
 def window_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, grid,
                 blend: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                 do_step: bool = True, eps_out: Optional[torch.Tensor] = None):

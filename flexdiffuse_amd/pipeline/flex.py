@@ -199,10 +199,17 @@ class FlexPipeline():
     def disable_attention_slicing(self):
         self.enable_attention_slicing(None)
 
+    def enable_vae_tiling(self, tile=64, stride=48, feather=None):
+        '''Decode and encode canvases larger than `tile` latent cells as overlapping VAE tiles at `stride`, blended over
+        `feather` cells (default tile - stride): AutoencoderKL.enable_tiling.  An approximation by construction.'''
+        self.vae.enable_tiling(tile, stride, feather)
+
+    def disable_vae_tiling(self):
+        self.vae.disable_tiling()
+
     def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
         '''latents -> device image tensor (B,3,H,W) fp32 in [0,1] (pipeline/flex.py:117-120).'''
-        img = self.vae.decode_nhwc(latents, scale=1.0 / VAE_SCALE)
-        return ops.nhwc_to_nchw(img.t, img.B, 3, img.H, img.W, 0.5, 0.5, True)
+        return self.vae.decode_image(latents, 1.0 / VAE_SCALE, 0.5, 0.5, True)
 
     def _decode_generic(self, latents: torch.Tensor) -> torch.Tensor:
         '''pipeline/flex.py:116-120 for any object with the diffusers surface `decode(z).sample`

@@ -67,6 +67,11 @@ def entity_from_row(row: Sequence[Any]) -> Optional[EntitySchema]:
 
 
 class Runner():
+    # opt-in (beyond the reference): VAE tiling of every request's decode and of an init image's encode
+    # (`FlexPipeline.enable_vae_tiling`): None (off), True (tile 64, stride 48) or a (tile, stride[, feather]) tuple in
+    # latent cells.  An attribute like `step_noise`; applied to the pipeline's VAE at the top of every run
+    vae_tiling = None
+
     def __init__(self, local: bool = True, device: str = 'cuda', *, sd_dir: Optional[str] = None,
                  clip_dir: Optional[str] = None, tokenizer_dir: Optional[str] = None,
                  state_dicts: Optional[Dict[str, dict]] = None, preset: str = 'sd15', seed_weights: int = 0,
@@ -131,6 +136,11 @@ class Runner():
              strength: float, debug: bool, mask_image=None):
         '''`batches` sequential pipeline calls on one generator stream -- the reference's only
         data-parallel axis (utils.py:90) -- and the grid of everything they produced.'''
+        # a pipeline around a foreign VAE (`_decode_generic`) has no tiling to switch off
+        if self.vae_tiling:
+            self.pipe.enable_vae_tiling(*(() if self.vae_tiling is True else self.vae_tiling))
+        elif getattr(getattr(self.pipe, 'vae', None), 'tiling', None) is not None:
+            self.pipe.disable_vae_tiling()
         images: List[Any] = []
         extra = {'mask_image': mask_image} if mask_image is not None else {}
         stochastic = self.step_noise or isinstance(self.pipe.scheduler, DPMSolverMultistepSDEScheduler)

@@ -9,13 +9,14 @@ runs as two batched MFMA GEMMs around a row softmax.
 from __future__ import annotations
 
 from types import SimpleNamespace
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence, Union
 
 import torch
 
 from . import hip, ops
 from .ops import Act
 from .weights import SD_VAE, VAEConfig, vae_param_shapes
+from .windows import Tiling, WindowGrid, tile_grid
 
 
 class _VRes:
@@ -60,6 +61,8 @@ class DiagonalGaussian():
 
 
 class AutoencoderKL():
+    tiling: Optional[Tiling] = None     # enable_tiling() / disable_tiling(); None: every method runs untiled
+
     def __init__(self, state_dict: Dict[str, torch.Tensor], config: VAEConfig = SD_VAE,
                  device='cuda', encoder: bool = True):
         hip.lib()
@@ -122,6 +125,36 @@ class AutoencoderKL():
     def to(self, device):
         return self
 
+    # ---- tiling ---------------------------------------------------------------------------
+    @property
+    def scale_factor(self) -> int:
+        '''Pixels per latent cell along an axis: 2^(levels - 1).'''
+        return 2 ** (len(self.cfg.block_out_channels) - 1)
+
+    def enable_tiling(self, tile: Union[int, Sequence[int]] = 64, stride: Union[int, Sequence[int]] = 48,
+                      feather: Union[None, int, Sequence[int]] = None):
+        '''Decode and encode canvases larger than `tile` latent cells as overlapping tiles at `stride`, blended over a ramp
+        of `feather` cells (default tile - stride) by one fd_tile_blend_f32 launch.  An approximation by construction:
+        GroupNorm statistics and the mid-block attention see one tile, not the canvas.'''
+        self.tiling = Tiling.of(tile, stride, feather)
+
+    def disable_tiling(self):
+        self.tiling = None
+
+    def tile_grid(self, h: int, w: int) -> Optional[WindowGrid]:
+        '''The tile grid of an (h, w)-cell canvas in latent cells, or None where the untiled path runs: tiling off, or a
+        canvas that fits one tile on both axes.'''
+        if self.tiling is None:
+            return None
+        g = tile_grid(h, w, self.tiling)
+        return None if g.count == 1 else g
+
+    def _sample_chunk(self, per_sample_pixels: int) -> int:
+        '''Samples per VAE pass that keep the widest activation (the full-resolution map of the narrowest level) at
+        <= 1 GiB: see decode_nhwc.'''
+        per_sample = per_sample_pixels * self.cfg.block_out_channels[0]      # elements (fp16)
+        return max(1, getattr(self, 'decode_chunk_elems', 1 << 29) // max(per_sample, 1))
+
     def _res(self, r: _VRes, x: Act) -> Act:
         h = ops.groupnorm(x, r.n1g, r.n1b, self.G, 1e-6, True)
         h = ops.conv2d(h, r.conv1)
@@ -149,9 +182,8 @@ class AutoencoderKL():
         32 images at 512x512, 14 at 768x768); the chunks keep it at <= 1 GiB.'''
         hip.require_device(z)
         B, _, hh, ww = z.shape
-        up = 2 ** (len(self.cfg.block_out_channels) - 1)
-        per_sample = hh * up * ww * up * self.cfg.block_out_channels[0]      # elements (fp16)
-        chunk = max(1, getattr(self, 'decode_chunk_elems', 1 << 29) // max(per_sample, 1))
+        up = self.scale_factor
+        chunk = self._sample_chunk(hh * up * ww * up)
         if B > chunk:
             parts = [self.decode_nhwc(z[i:i + chunk], scale) for i in range(0, B, chunk)]
             return Act(torch.cat([p.t for p in parts]), B, parts[0].H, parts[0].W)
@@ -172,12 +204,30 @@ class AutoencoderKL():
         h = ops.groupnorm(h, self.d_out_g, self.d_out_b, self.G, 1e-6, True)
         return ops.conv2d(h, self.d_conv_out, out_f32=True)
 
+    def decode_image(self, z: torch.Tensor, scale: float = 1.0, a: float = 1.0, b: float = 0.0,
+                     clamp01: bool = False) -> torch.Tensor:
+        '''(B,4,h,w) fp32 latents (multiplied by `scale`) -> (B,3,H,W) fp32 image, y = x*a + b, optionally clamped to
+        [0, 1].  Untiled: decode_nhwc and the layout kernel.  Tiled: the latents gathered into the tile batch
+        (B Tn, 4, th, tw), decode_nhwc on that batch (its sample chunks bound the activations), one fd_tile_blend_f32.'''
+        hip.require_device(z)
+        B, L, hh, ww = z.shape
+        C = self.cfg.out_channels
+        g = self.tile_grid(hh, ww)
+        if g is None:
+            img = self.decode_nhwc(z, scale)
+            return ops.nhwc_to_nchw(img.t, img.B, C, img.H, img.W, a, b, clamp01)
+        tiles = torch.empty((B * g.count, L, g.h, g.w), dtype=torch.float32, device=z.device)
+        ops.window_gather(z.to(torch.float32).contiguous(), tiles, B, L, g.args)
+        img = self.decode_nhwc(tiles, scale)
+        f = self.scale_factor
+        return ops.tile_blend(img.t, B, C, g.scaled(f).args, self.tiling.feather_of(f), a, b, clamp01)
+
     def decode(self, z: torch.Tensor):
-        img = self.decode_nhwc(z)
-        return SimpleNamespace(sample=ops.nhwc_to_nchw(img.t, img.B, self.cfg.out_channels, img.H, img.W))
+        return SimpleNamespace(sample=self.decode_image(z))
 
     # ---- encode ---------------------------------------------------------------------------
-    def encode(self, x: torch.Tensor):
+    def encode_moments_nhwc(self, x: torch.Tensor) -> Act:
+        '''(B,3,H,W) fp32 image -> the NHWC fp32 moments Act [B*h*w][2L] (mean | logvar, unclamped).'''
         if not self.has_encoder:
             raise RuntimeError('this AutoencoderKL was built without its encoder')
         hip.require_device(x)
@@ -192,8 +242,33 @@ class AutoencoderKL():
         h = self._res(self.e_mid[2], h)
         h = ops.groupnorm(h, self.e_out_g, self.e_out_b, self.G, 1e-6, True)
         h = ops.conv2d(h, self.e_conv_out)
-        m = ops.gemm(h.t, self.quant, out_f32=True)
+        return Act(ops.gemm(h.t, self.quant, out_f32=True), h.B, h.H, h.W)
+
+    def encode_moments(self, x: torch.Tensor) -> torch.Tensor:
+        '''(B,3,H,W) fp32 image -> (B,2L,h,w) fp32 moments (mean | logvar, unclamped).  Tiled: the image gathered into the
+        tile batch on the pixel grid, the moments of that batch in decode's sample chunks, one fd_tile_blend_f32 in latent
+        cells.'''
+        if not self.has_encoder:
+            raise RuntimeError('this AutoencoderKL was built without its encoder')
+        hip.require_device(x)
+        B, Cin, H, W = x.shape
+        L2, f = 2 * self.cfg.latent_channels, self.scale_factor
+        g = self.tile_grid(H // f, W // f)
+        if g is None:
+            m = self.encode_moments_nhwc(x)
+            return ops.nhwc_to_nchw(m.t, m.B, L2, m.H, m.W)
+        if H % f or W % f:
+            raise ValueError(f'tiled encode of a {H} x {W} image: the extents must be multiples of {f}')
+        gp = g.scaled(f)
+        tiles = torch.empty((B * g.count, Cin, gp.h, gp.w), dtype=torch.float32, device=x.device)
+        ops.window_gather(x.to(torch.float32).contiguous(), tiles, B, Cin, gp.args)
+        chunk = self._sample_chunk(gp.h * gp.w)
+        parts = [self.encode_moments_nhwc(tiles[i:i + chunk]).t for i in range(0, len(tiles), chunk)]
+        m = parts[0] if len(parts) == 1 else torch.cat(parts)
+        return ops.tile_blend(m, B, L2, g.args, self.tiling.feather_of())
+
+    def encode(self, x: torch.Tensor):
+        mom = self.encode_moments(x)
         L = self.cfg.latent_channels
-        mom = ops.nhwc_to_nchw(m, h.B, 2 * L, h.H, h.W)
         mean, logvar = mom[:, :L].contiguous(), mom[:, L:].clamp(-30.0, 20.0).contiguous()
         return SimpleNamespace(latent_dist=DiagonalGaussian(mean, logvar))

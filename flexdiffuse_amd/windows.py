@@ -66,6 +66,10 @@ class WindowGrid():
         oys, oxs = axis_offsets(self.H, self.h, self.stride_y), axis_offsets(self.W, self.w, self.stride_x)
         return [(oy, ox) for oy in oys for ox in oxs]
 
+    def scaled(self, f: int) -> 'WindowGrid':
+        '''This grid with every extent times f (latent cells -> pixels): the count rule is scale-invariant.'''
+        return WindowGrid(self.H * f, self.W * f, self.h * f, self.w * f, self.stride_y * f, self.stride_x * f, self.ny, self.nx)
+
 
 def window_grid(H: int, W: int, h: int, w: int, stride_y: int, stride_x: int, multiple: int = 1) -> WindowGrid:
     '''The grid of (h, w) windows at (stride_y, stride_x) over an (H, W) canvas.  `multiple`: what the UNet asks of a latent's
@@ -93,6 +97,40 @@ def pair(v: Union[int, Sequence[int]]) -> Tuple[int, int]:
         return v, v
     a, b = v
     return int(a), int(b)
+
+
+@dataclass(frozen=True)
+class Tiling():
+    '''VAE tiling (AutoencoderKL.enable_tiling): (tile, stride, feather) per axis (y, x), in latent cells.'''
+    tile: Tuple[int, int]
+    stride: Tuple[int, int]
+    feather: Tuple[int, int]
+
+    @staticmethod
+    def of(tile=64, stride=48, feather=None) -> 'Tiling':
+        '''From ints or pairs; feather None: tile - stride (at least 1).  ValueError unless 1 <= stride <= tile and
+        feather >= 1 on both axes.'''
+        tile, stride = pair(tile), pair(stride)
+        feather = tuple(max(t - d, 1) for t, d in zip(tile, stride)) if feather is None else pair(feather)
+        for t, d, f in zip(tile, stride, feather):
+            if not 1 <= d <= t:
+                raise ValueError(f'need 1 <= stride <= tile, got stride {d}, tile {t}: a stride above the tile would leave gaps')
+            if f < 1:
+                raise ValueError(f'feather should be at least 1 cell but is {f}')
+        return Tiling(tile, stride, feather)
+
+    def feather_of(self, f: int = 1) -> Tuple[int, int]:
+        '''The feathers fd_tile_blend_f32 takes: this tiling's, times f (cells -> pixels).'''
+        return self.feather[0] * f, self.feather[1] * f
+
+
+def tile_grid(H: int, W: int, tiling: Tiling) -> WindowGrid:
+    '''The grid of VAE tiles over an (H, W)-cell canvas: windows of the tiling's extent at its stride, the last snapped to the
+    edge.  On an axis where the canvas is not larger than the tile the tile extent is the canvas extent and there is one
+    tile.  ValueError past 16 tiles on an axis (axis_count).'''
+    h, w = min(tiling.tile[0], int(H)), min(tiling.tile[1], int(W))
+    sy, sx = min(tiling.stride[0], h), min(tiling.stride[1], w)
+    return WindowGrid(int(H), int(W), h, w, sy, sx, axis_count(int(H), h, sy), axis_count(int(W), w, sx))
 
 
 def window_context(uncond: torch.Tensor, embeds: torch.Tensor, count: int, cfg: bool) -> torch.Tensor:

@@ -707,6 +707,22 @@ int fd_window_multistep_step_f32(float* x, float* windows_out, const float* eps_
                                  int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance,
                                  float p, float q, float a, float w0, float w1, float k1, float k2, float sn, uint64_t seed,
                                  int64_t sample_offset, int draw, void* stream);
+/* Tiled VAE decode / encode (additive; FD_ABI_VERSION stays 12): the VAE runs on a batch of overlapping tiles of the model's
+ * own size -- the grid of fd_window_gather_f32, same rule, same batch order -- and this one launch puts the tile outputs
+ * together.  tiles: NHWC fp32, the row of (sample b, tile t = iy nx + ix, ly, lx) is ((b ny nx + t) h + ly) w + lx, row
+ * stride ld >= C.  out: (B, C, H, W) NCHW fp32.  All extents are in the units of out (pixels for a decode, latent cells for an
+ * encode).  Per canvas element (b, c, y, x), every operation a separately rounded fp32 one:
+ *   acc = 0, wsum = 0 ;  for every tile covering the element, in ascending (iy, ix) order, v its value there:
+ *     wgt = r_y(ly) r_x(lx),  r(l) = min(l + 1, E - l, F), E the tile extent and F the feather of that axis (small integers:
+ *     the weight is exact) ;  acc = acc + wgt v ;  wsum = wsum + wgt
+ *   u = v where exactly one tile covers the element (an exact branch), else acc / wsum
+ *   y = u a + b (a product, then a sum) ;  clamp01: y = min(max(y, 0), 1)
+ * F = 1 is the plain average, F >= E / 2 the full tent.  With a a power of two a one-tile grid gives the bits of
+ * fd_nhwc_f32_to_nchw_f32.  One thread owns one canvas pixel and its C channels; a tile pixel is read as float4 loads when
+ * ld % 4 == 0 and tiles is 16-byte aligned, as scalars otherwise.  No atomics: every element of out is written exactly once.
+ * FD_EINVAL: the grid's errors; NULL tiles or out; ld < C; a feather below 1; out overlapping tiles. */
+int fd_tile_blend_f32(const float* tiles, float* out, int B, int C, int ld, int H, int W, int h, int w, int stride_y,
+                      int stride_x, int ny, int nx, int feather_y, int feather_x, float a, float b, int clamp01, void* stream);
 /* Contiguous casts: fp32 -> fp16 rounds to nearest even (overflow to inf from 65520 on), fp16 -> fp32 is exact. */
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
