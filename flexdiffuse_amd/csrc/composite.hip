@@ -6,6 +6,7 @@
 // rectangle (weight = blend inside the box) gives the bits of the fd_region_blend_f32 +
 // fd_cfg_ddim_step_f32 chain.
 #include "latent_step.h"
+#include "step_args.h"
 
 // eps rows: block r of E = cfg + 1 + n blocks ([uncond] [background] [entity 0] ... [entity n-1]),
 // sample b, pixel p -> row (r * B + b) * HW + p, row stride ld.  One thread owns one (b, p) and
@@ -53,10 +54,10 @@ extern "C" int fd_composite_step_f32(float* x, const float* eps_nhwc, const floa
     FD_PLAN(fd_composite_step_f32(x, eps_nhwc, weights, eps_out, B, C, HW, ld, n_entities, cfg, guidance, c1, c2, c3, c4,
                                   v_prediction, do_step, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(eps_nhwc && B > 0 && C > 0 && HW > 0 && ld >= C && n_entities >= 0, FD_EINVAL,
-                 "fd_composite_step_f32: args");
+    FD_CHECK_ARG(eps_nhwc && (!do_step || x), FD_EINVAL, "fd_composite_step_f32: x or eps_nhwc is null");
+    FD_TRY(fd_step_sizes("fd_composite_step_f32", B, C, HW, ld, true));
+    FD_CHECK_ARG(n_entities >= 0, FD_EINVAL, "fd_composite_step_f32: sizes: n_entities %d", n_entities);
     FD_CHECK_ARG(n_entities == 0 || weights, FD_EINVAL, "fd_composite_step_f32: weights are null");
-    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_composite_step_f32: x is null");
     const int blocks = fd_grid1d((size_t)B * HW, 2048);
     const bool vec = C % 4 == 0 && ld % 4 == 0 && (uintptr_t)eps_nhwc % 16 == 0;
     if (vec)

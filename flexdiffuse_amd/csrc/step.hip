@@ -29,6 +29,7 @@
 // (C = 1, ld = 1).  The coefficients come from the host (the schedulers' step_coefficients, inpaint.known_coefficients).
 #include "latent_step.h"
 #include "philox.h"
+#include "step_args.h"
 
 // Optional pointers are NULL when unused (uniform across the grid).  co: DDIM c1 c2 c3 c4 | multistep p q a w0 w1.
 struct FdStepArgs {
@@ -226,36 +227,129 @@ __global__ __launch_bounds__(FD_RESCALE_THREADS) void k_latent_step_rescale(cons
     }
 }
 
-// V = 4 when HW % 4 == 0 (with noise: per % 4 == 0 too) and every NCHW pointer the kernel will touch is 16-byte aligned,
-// else V = 1; grid; launch.  sn == 0 launches the kernels without the noise stage: today's bits.  n_ent > 0 launches the
-// COMP instantiations (the weight maps join the aligned pointers); n_ent == 0 the kernels every fd_cfg_* entry point launches.
-static int fd_latent_step(int update, const FdStepArgs& a, void* stream) {
+// ---- the host path: fill, check, select, launch -- each written once ------------------------------------------------------
+// A front names the fields of an FdStepArgs it sets (every other one is value-initialised: NULL / 0) and calls fd_step_run.
+// fd_step_check reads its rules off the fields that are set; what a front asks beyond them is one of these flags, its noise
+// address an FdStepNoise, its rescale an FdStepRescale.  Which of two simultaneous violations is reported is not part of the
+// contract.
+enum {
+    FD_EPS_OPTIONAL = 1,       // eps_nhwc == NULL is the blend alone on the x' that x holds (fd_cfg_ddim_masked_step_f32)
+    FD_BLEND_REQUIRED = 2,     // ... and z0, noise and mask are what that front is for
+    FD_NOISE_ALWAYS = 4,       // the noise address is checked at sn == 0 too, as the fronts that carry this have always done
+    FD_EPS_OUT_ON_X = 8,       // eps_out may be x (a thread overwrites its own elements): fd_cfg_ddim_step_f32 has always taken it
+};
+struct FdStepNoise {
+    uint64_t seed;
+    int64_t sample_offset;
+    int per, draw;             // per: ignored by the rescaled forms, whose statistics fix a sample as C HW elements
+};
+struct FdStepRescale {
+    float phi;
+    float* scale_out;
+};
+
+// Every rule of the family, once; fills a.nz_addr.  Every check precedes the launch.
+static int fd_step_check(const char* who, int update, FdStepArgs& a, unsigned flags, const FdStepNoise* nz,
+                         const FdStepRescale* rs) {
+    // required pointers (the CFG combine alone, -> eps_out, touches no x)
+    FD_CHECK_ARG(a.eps || (flags & FD_EPS_OPTIONAL), FD_EINVAL, "%s: eps_nhwc is null", who);
+    FD_CHECK_ARG(a.x || (update == FD_STEP_NONE && !a.mask), FD_EINVAL, "%s: x is null", who);
+    FD_CHECK_ARG(a.m0_out || update != FD_STEP_MULTISTEP, FD_EINVAL, "%s: m0_out is null", who);
+    FD_CHECK_ARG(!(flags & FD_BLEND_REQUIRED) || (a.z0 && a.nz && a.mask), FD_EINVAL, "%s: z0, noise or mask is null", who);
+    FD_TRY(fd_step_sizes(who, a.B, a.C, a.HW, a.ld, a.eps != nullptr));
+    if (rs) {                                                        // k_latent_step_rescale counts a sample in 32 bits
+        FD_CHECK_ARG((unsigned long long)a.C * a.HW <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * HW past 2^31", who);
+        FD_CHECK_ARG(rs->phi >= 0.f && rs->phi <= 1.f, FD_EINVAL, "%s: rescale %g is outside [0, 1]", who, (double)rs->phi);
+        FD_CHECK_ARG(update != FD_STEP_NONE || (a.eps_out && !a.mask && a.sn == 0.f), FD_EINVAL,
+                     "%s: the combine-only form needs eps_out and takes neither mask nor sigma", who);
+    }
+    if (update == FD_STEP_LINEAR) {
+        FD_CHECK_ARG(a.form == 0 || a.form == 1, FD_EINVAL, "%s: form %d is neither 0 (PLMS) nor 1 (K-LMS)", who, a.form);
+        FD_CHECK_ARG(a.n_prev >= 0 && a.n_prev <= 3, FD_EINVAL, "%s: n_prev %d is outside 0..3", who, a.n_prev);
+        const float* const rows[3] = {a.m1, a.h2, a.h3};
+        for (int k = 0; k < a.n_prev; ++k)
+            FD_CHECK_ARG(rows[k], FD_EINVAL, "%s: history row h%d is null with n_prev %d", who, k + 1, a.n_prev);
+        FD_CHECK_ARG(a.form == 0 || (a.m0_out && !a.x_src && !a.x_keep), FD_EINVAL,
+                     "%s: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out", who);
+    }
+    FD_TRY(fd_entity_args(who, a.wmap, a.n_ent));
+    FD_TRY(fd_blend_args(who, a.x, a.z0, a.nz, a.mask, "latents"));
+    // no output on a buffer the launch still reads (x, the history rows, x_src, the known region) or on another output
+    FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x || (flags & FD_EPS_OUT_ON_X), FD_EINVAL, "%s: eps_out aliases the latents", who);
+    const float* const reads[7] = {a.x, a.m1, a.h2, a.h3, a.x_src, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr};
+    float* const outs[2] = {a.m0_out, a.x_keep};
+    for (int o = 0; o < 2; ++o)
+        for (int r = 0; outs[o] && r < (update == FD_STEP_LINEAR ? 7 : 2); ++r)      // multistep: m0_out against x and m1
+            FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "%s: m0_out / h_out / x_keep_out alias the latents or a row that is read", who);
+    FD_CHECK_ARG(!a.m0_out || a.m0_out != a.x_keep, FD_EINVAL, "%s: h_out and x_keep_out alias each other", who);
+    FD_CHECK_ARG(!a.x_scaled || (a.x_scaled != a.x && a.x_scaled != a.m0_out && a.x_scaled != a.x_keep), FD_EINVAL,
+                 "%s: x_scaled_out aliases the latents or another output", who);
+    if (nz && (a.sn != 0.f || (flags & FD_NOISE_ALWAYS)))
+        FD_TRY(fd_noise_addr(who, nz->seed, nz->sample_offset, rs ? a.C * a.HW : nz->per, nz->draw, 0,
+                             (unsigned long long)a.B * a.C * a.HW, &a.nz_addr));
+    return FD_OK;
+}
+
+// The vector rule of k_latent_step and k_latent_step_rescale, a pure function of (update, a): V = 4 when HW % 4 == 0 (with the
+// noise stage: per % 4 == 0 too) and every NCHW pointer the kernel will touch is 16-byte aligned, else V = 1.  sn == 0 runs
+// the kernels without the noise stage.  This is the union of the two rules the kernels used to have: the rescaled one left
+// out the linear forms' pointers and the weight maps, which its fronts never set (NULL adds nothing to `bases`).
+struct FdStepVec {
+    int vec, noise;
+};
+static FdStepVec fd_step_vec(int update, const FdStepArgs& a) {
     uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
     if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
     if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
-    // (the linear forms' pointers; NULL on every other update)
     bases |= (uintptr_t)a.h2 | (uintptr_t)a.h3 | (uintptr_t)a.x_src | (uintptr_t)a.x_keep | (uintptr_t)a.x_scaled;
     if (a.n_ent > 0) bases |= (uintptr_t)a.wmap;
     const int noise = update != FD_STEP_NONE && a.sn != 0.f;
-    const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
-    static void (*const comp_kernels[2][2][4])(const FdStepArgs) = {
-        {{nullptr, k_latent_step<1, FD_STEP_DDIM, false, true>, k_latent_step<1, FD_STEP_MULTISTEP, false, true>,
-          k_latent_step<1, FD_STEP_LINEAR, false, true>},
-         {nullptr, k_latent_step<4, FD_STEP_DDIM, false, true>, k_latent_step<4, FD_STEP_MULTISTEP, false, true>,
-          k_latent_step<4, FD_STEP_LINEAR, false, true>}},
-        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true, true>, k_latent_step<1, FD_STEP_MULTISTEP, true, true>, nullptr},
-         {nullptr, k_latent_step<4, FD_STEP_DDIM, true, true>, k_latent_step<4, FD_STEP_MULTISTEP, true, true>, nullptr}}};
-    static void (*const kernels[2][2][4])(const FdStepArgs) = {
-        {{k_latent_step<1, FD_STEP_NONE, false>, k_latent_step<1, FD_STEP_DDIM, false>, k_latent_step<1, FD_STEP_MULTISTEP, false>,
-          k_latent_step<1, FD_STEP_LINEAR, false>},
-         {k_latent_step<4, FD_STEP_NONE, false>, k_latent_step<4, FD_STEP_DDIM, false>, k_latent_step<4, FD_STEP_MULTISTEP, false>,
-          k_latent_step<4, FD_STEP_LINEAR, false>}},
-        {{nullptr, k_latent_step<1, FD_STEP_DDIM, true>, k_latent_step<1, FD_STEP_MULTISTEP, true>, nullptr},
-         {nullptr, k_latent_step<4, FD_STEP_DDIM, true>, k_latent_step<4, FD_STEP_MULTISTEP, true>, nullptr}}};
-    const size_t groups = (size_t)a.B * a.C * a.HW / (vec ? 4 : 1);
-    hipLaunchKernelGGL((a.n_ent > 0 ? comp_kernels : kernels)[noise][vec][update], dim3(fd_grid1d(groups, 2048)), dim3(256), 0,
-                       (hipStream_t)stream, a);
-    FD_CHECK_LAUNCH("k_latent_step");
+    return {a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0), noise};
+}
+
+// The kernel of (rescale, comp, noise, vec, update), or NULL where none is instantiated -- a noise stage without an update or
+// on the linear update, composition without an update, rescale on the linear update or together with composition: the caller
+// refuses those before the launch.  Rows in the order [composition | plain | rescale][noise][vec][update].
+static const void* fd_step_kernel(bool rescale, bool comp, bool noise, bool vec, int update) {
+#define FD_K(...) ((const void*)(__VA_ARGS__))
+    static const void* const kernels[3][2][2][4] = {
+        {{{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, false, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, false, true>),
+           FD_K(k_latent_step<1, FD_STEP_LINEAR, false, true>)},
+          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, false, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, false, true>),
+           FD_K(k_latent_step<4, FD_STEP_LINEAR, false, true>)}},
+         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true, true>), nullptr},
+          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true, true>), nullptr}}},
+        {{{FD_K(k_latent_step<1, FD_STEP_NONE, false>), FD_K(k_latent_step<1, FD_STEP_DDIM, false>),
+           FD_K(k_latent_step<1, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<1, FD_STEP_LINEAR, false>)},
+          {FD_K(k_latent_step<4, FD_STEP_NONE, false>), FD_K(k_latent_step<4, FD_STEP_DDIM, false>),
+           FD_K(k_latent_step<4, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<4, FD_STEP_LINEAR, false>)}},
+         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true>), nullptr},
+          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true>), nullptr}}},
+        {{{FD_K(k_latent_step_rescale<1, FD_STEP_NONE, false>), FD_K(k_latent_step_rescale<1, FD_STEP_DDIM, false>),
+           FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, false>), nullptr},
+          {FD_K(k_latent_step_rescale<4, FD_STEP_NONE, false>), FD_K(k_latent_step_rescale<4, FD_STEP_DDIM, false>),
+           FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, false>), nullptr}},
+         {{nullptr, FD_K(k_latent_step_rescale<1, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, true>), nullptr},
+          {nullptr, FD_K(k_latent_step_rescale<4, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, true>), nullptr}}}};
+#undef FD_K
+    if ((rescale && comp) || update < FD_STEP_NONE || update > FD_STEP_LINEAR) return nullptr;
+    return kernels[rescale ? 2 : comp ? 0 : 1][noise][vec][update];
+}
+
+// check; vector rule; kernel; grid (k_latent_step: grid-stride over the groups | rescaled: one workgroup per sample); launch
+static int fd_step_run(const char* who, int update, FdStepArgs& a, void* stream, unsigned flags = 0,
+                       const FdStepNoise* nz = nullptr, const FdStepRescale* rs = nullptr) {
+    FD_TRY(fd_step_check(who, update, a, flags, nz, rs));
+    const FdStepVec v = fd_step_vec(update, a);
+    const void* const kernel = fd_step_kernel(rs != nullptr, a.n_ent > 0, v.noise, v.vec, update);
+    FD_CHECK_ARG(kernel, FD_EINVAL, "%s: no kernel for update %d with rescale %d, entities %d, noise %d", who, update,
+                 rs != nullptr, a.n_ent, v.noise);
+    FdStepRescale r = rs ? *rs : FdStepRescale{};
+    void* params[3] = {&a, &r.phi, &r.scale_out};                    // k_latent_step takes the first alone
+    const size_t groups = (size_t)a.B * a.C * a.HW / (v.vec ? 4 : 1);
+    hipLaunchKernel(kernel, rs ? dim3(a.B) : dim3(fd_grid1d(groups, 2048)), rs ? dim3(FD_RESCALE_THREADS) : dim3(256), params, 0,
+                    (hipStream_t)stream);
+    FD_CHECK_LAUNCH(rs ? "k_latent_step_rescale" : "k_latent_step");
     return FD_OK;
 }
 
@@ -264,11 +358,9 @@ extern "C" int fd_cfg_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_
                                     void* stream) {
     FD_PLAN(fd_cfg_ddim_step_f32(x, eps_nhwc, eps_out, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4, v_prediction, do_step, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(eps_nhwc && B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_ddim_step_f32: args");
-    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_cfg_ddim_step_f32: x is null");
-    const FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, nullptr, nullptr, nullptr, B, C, HW, ld, cfg, v_prediction,
-                          guidance, {c1, c2, c3, c4, 0.f}, 1.f, 0.f, 0.f, {}};
-    return fd_latent_step(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
+    FdStepArgs a = {.x = x, .eps = eps_nhwc, .eps_out = eps_out, .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg,
+                    .vpred = v_prediction, .g = guidance, .co = {c1, c2, c3, c4}};
+    return fd_step_run("fd_cfg_ddim_step_f32", do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream, FD_EPS_OUT_ON_X);
 }
 
 extern "C" int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, const float* z0, const float* noise,
@@ -278,12 +370,10 @@ extern "C" int fd_cfg_ddim_masked_step_f32(float* x, const float* eps_nhwc, cons
     FD_PLAN(fd_cfg_ddim_masked_step_f32(x, eps_nhwc, z0, noise, mask, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4,
                                         v_prediction, k1, k2, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && z0 && noise && mask, FD_EINVAL, "fd_cfg_ddim_masked_step_f32: x, z0, noise or mask is null");
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && (!eps_nhwc || ld >= C), FD_EINVAL, "fd_cfg_ddim_masked_step_f32: sizes");
-    FD_CHECK_ARG(x != z0 && x != noise, FD_EINVAL, "fd_cfg_ddim_masked_step_f32: z0 / noise alias the latents");
-    const FdStepArgs a = {x, eps_nhwc, nullptr, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
-                          guidance, {c1, c2, c3, c4, 0.f}, k1, k2, 0.f, {}};
-    return fd_latent_step(eps_nhwc ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
+    FdStepArgs a = {.x = x, .eps = eps_nhwc, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg,
+                    .vpred = v_prediction, .g = guidance, .co = {c1, c2, c3, c4}, .k1 = k1, .k2 = k2};
+    return fd_step_run("fd_cfg_ddim_masked_step_f32", eps_nhwc ? FD_STEP_DDIM : FD_STEP_NONE, a, stream,
+                       FD_EPS_OPTIONAL | FD_BLEND_REQUIRED);
 }
 
 extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
@@ -293,76 +383,13 @@ extern "C" int fd_cfg_multistep_step_f32(float* x, const float* eps_nhwc, float*
     FD_PLAN(fd_cfg_multistep_step_f32(x, eps_nhwc, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, guidance, p, q, a, w0,
                                       w1, k1, k2, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "fd_cfg_multistep_step_f32: x, eps_nhwc or m0_out is null");
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_multistep_step_f32: sizes");
-    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_cfg_multistep_step_f32: m0_out aliases the latents or m1");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_multistep_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_multistep_step_f32: z0 / noise alias the latents");
-    const FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
-                          guidance, {p, q, a, w0, w1}, k1, k2, 0.f, {}};
-    return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C,
+                    .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .co = {p, q, a, w0, w1}, .k1 = k1, .k2 = k2};
+    return fd_step_run("fd_cfg_multistep_step_f32", FD_STEP_MULTISTEP, s, stream);
 }
 
 // PLMS (form 0) and K-LMS (form 1): CFG, the history write, the linear multistep update over up to three earlier history rows,
-// the blend and (K-LMS) the next step's scaled model input.  Every check precedes the launch.
-// the checks the composite fronts add to their siblings'; eps_nhwc then holds (cfg + 1 + n_entities) B HW rows
-static int fd_composite_args(const char* who, const float* weights, int n_entities) {
-    FD_CHECK_ARG(n_entities >= 0, FD_EINVAL, "%s: n_entities %d is negative", who, n_entities);
-    FD_CHECK_ARG(n_entities == 0 || weights, FD_EINVAL, "%s: weights are null with n_entities %d", who, n_entities);
-    return FD_OK;
-}
-
-// the body of fd_cfg_linear_multistep_step_f32 and of its composite front (weights, n_entities: NULL, 0 for the first)
-static int fd_linear_multistep_step(const char* who, float* x, const float* eps_nhwc, const float* weights, int n_entities,
-                                    int form, int n_prev, const float* h1, const float* h2, const float* h3, float* h_out,
-                                    float* x_keep_out, const float* x_src, float* x_scaled_out, const float* z0,
-                                    const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
-                                    float guidance, float w0, float w1, float w2, float w3, float a0, float a1, float a2,
-                                    float scale, float k1, float k2, void* stream) {
-    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "%s: x or eps_nhwc is null", who);
-    FD_CHECK_ARG(form == 0 || form == 1, FD_EINVAL, "%s: form %d is neither 0 (PLMS) nor 1 (K-LMS)", who, form);
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
-    FD_CHECK_ARG(n_prev >= 0 && n_prev <= 3, FD_EINVAL, "%s: n_prev %d is outside 0..3", who, n_prev);
-    const float* const rows[3] = {h1, h2, h3};
-    for (int k = 0; k < n_prev; ++k)
-        FD_CHECK_ARG(rows[k], FD_EINVAL, "%s: history row h%d is null with n_prev %d", who, k + 1, n_prev);
-    FD_CHECK_ARG(form == 0 || (h_out && !x_src && !x_keep_out), FD_EINVAL,
-                 "%s: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out", who);
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
-    // the rows the launch reads besides x and eps
-    const float* const reads[6] = {n_prev >= 1 ? h1 : nullptr, n_prev >= 2 ? h2 : nullptr, n_prev >= 3 ? h3 : nullptr, x_src,
-                                   mask ? z0 : nullptr, mask ? noise : nullptr};
-    float* const outs[2] = {h_out, x_keep_out};
-    for (int o = 0; o < 2; ++o) {
-        if (!outs[o]) continue;
-        FD_CHECK_ARG(outs[o] != x, FD_EINVAL, "%s: h_out / x_keep_out alias the latents", who);
-        for (int r = 0; r < 6; ++r)
-            FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "%s: h_out / x_keep_out alias a row that is read", who);
-    }
-    FD_CHECK_ARG(!h_out || h_out != x_keep_out, FD_EINVAL, "%s: h_out and x_keep_out alias each other", who);
-    FD_CHECK_ARG(!x_scaled_out || (x_scaled_out != x && x_scaled_out != h_out && x_scaled_out != x_keep_out), FD_EINVAL,
-                 "%s: x_scaled_out aliases the latents or another output", who);
-    const int rc = fd_composite_args(who, weights, n_entities);
-    if (rc != FD_OK) return rc;
-    FdStepArgs s = {x, eps_nhwc, nullptr, h_out, n_prev >= 1 ? h1 : nullptr, z0, noise, mask, B, C, HW, ld, cfg, 0,
-                    guidance, {0.f, 0.f, 0.f, 0.f, 0.f}, k1, k2, 0.f, {}};
-    s.h2 = n_prev >= 2 ? h2 : nullptr;
-    s.h3 = n_prev >= 3 ? h3 : nullptr;
-    s.x_src = x_src;
-    s.x_keep = x_keep_out;
-    s.x_scaled = x_scaled_out;
-    s.form = form;
-    s.n_prev = n_prev;
-    const float lw[4] = {w0, w1, w2, w3}, la[3] = {a0, a1, a2};
-    for (int k = 0; k < 4; ++k) s.lw[k] = lw[k];
-    for (int k = 0; k < 3; ++k) s.la[k] = la[k];
-    s.ls = scale;
-    s.wmap = weights;
-    s.n_ent = n_entities;
-    return fd_latent_step(FD_STEP_LINEAR, s, stream);
-}
-
+// the blend and (K-LMS) the next step's scaled model input.
 extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc, int form, int n_prev, const float* h1,
                                                 const float* h2, const float* h3, float* h_out, float* x_keep_out,
                                                 const float* x_src, float* x_scaled_out, const float* z0,
@@ -373,9 +400,11 @@ extern "C" int fd_cfg_linear_multistep_step_f32(float* x, const float* eps_nhwc,
                                              noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2, w3, a0, a1, a2, scale, k1,
                                              k2, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    return fd_linear_multistep_step("fd_cfg_linear_multistep_step_f32", x, eps_nhwc, nullptr, 0, form, n_prev, h1, h2, h3, h_out,
-                                    x_keep_out, x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2,
-                                    w3, a0, a1, a2, scale, k1, k2, stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = h_out, .m1 = n_prev >= 1 ? h1 : nullptr, .z0 = z0, .nz = noise, .mask = mask,
+                    .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .k1 = k1, .k2 = k2,
+                    .h2 = n_prev >= 2 ? h2 : nullptr, .h3 = n_prev >= 3 ? h3 : nullptr, .x_src = x_src, .x_keep = x_keep_out,
+                    .x_scaled = x_scaled_out, .form = form, .n_prev = n_prev, .lw = {w0, w1, w2, w3}, .la = {a0, a1, a2}, .ls = scale};
+    return fd_step_run("fd_cfg_linear_multistep_step_f32", FD_STEP_LINEAR, s, stream);
 }
 
 // ---- the stochastic forms ------------------------------------------------------------------------------------------
@@ -388,39 +417,10 @@ extern "C" int fd_cfg_ddim_noise_step_f32(float* x, const float* eps_nhwc, const
     FD_PLAN(fd_cfg_ddim_noise_step_f32(x, eps_nhwc, z0, noise, mask, B, C, HW, ld, cfg, guidance, c1, c2, c3, c4,
                                        v_prediction, k1, k2, sigma, seed, sample_offset, per, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_cfg_ddim_noise_step_f32: x or eps_nhwc is null");
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "fd_cfg_ddim_noise_step_f32: sizes");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_ddim_noise_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_ddim_noise_step_f32: z0 / noise alias the latents");
-    FdStepArgs a = {x, eps_nhwc, nullptr, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
-                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
-    const int rc = fd_noise_addr("fd_cfg_ddim_noise_step_f32", seed, sample_offset, per, draw, 0,
-                                 (unsigned long long)B * C * HW, &a.nz_addr);
-    if (rc != FD_OK) return rc;
-    return fd_latent_step(FD_STEP_DDIM, a, stream);
-}
-
-// the body of fd_cfg_multistep_noise_step_f32 and of the composite front (weights, n_entities: NULL, 0 for the first)
-static int fd_multistep_noise_step(const char* who, float* x, const float* eps_nhwc, const float* weights, int n_entities,
-                                   float* m0_out, const float* m1, const float* z0, const float* noise, const float* mask,
-                                   int B, int C, int HW, int ld, int cfg, float guidance, float p, float q, float a, float w0,
-                                   float w1, float k1, float k2, float sn, uint64_t seed, int64_t sample_offset, int per,
-                                   int draw, void* stream) {
-    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "%s: x, eps_nhwc or m0_out is null", who);
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
-    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "%s: m0_out aliases the latents or m1", who);
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
-    const int rw = fd_composite_args(who, weights, n_entities);
-    if (rw != FD_OK) return rw;
-    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, 0,
-                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
-    const int rc = fd_noise_addr(who, seed, sample_offset, per, draw, 0,
-                                 (unsigned long long)B * C * HW, &s.nz_addr);
-    if (rc != FD_OK) return rc;
-    s.wmap = weights;
-    s.n_ent = n_entities;
-    return fd_latent_step(FD_STEP_MULTISTEP, s, stream);
+    FdStepArgs a = {.x = x, .eps = eps_nhwc, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg,
+                    .vpred = v_prediction, .g = guidance, .co = {c1, c2, c3, c4}, .k1 = k1, .k2 = k2, .sn = sigma};
+    const FdStepNoise nz = {seed, sample_offset, per, draw};
+    return fd_step_run("fd_cfg_ddim_noise_step_f32", FD_STEP_DDIM, a, stream, FD_NOISE_ALWAYS, &nz);
 }
 
 extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
@@ -432,8 +432,10 @@ extern "C" int fd_cfg_multistep_noise_step_f32(float* x, const float* eps_nhwc, 
     FD_PLAN(fd_cfg_multistep_noise_step_f32(x, eps_nhwc, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg, guidance, p, q,
                                             a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    return fd_multistep_noise_step("fd_cfg_multistep_noise_step_f32", x, eps_nhwc, nullptr, 0, m0_out, m1, z0, noise, mask, B, C,
-                                   HW, ld, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C,
+                    .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .co = {p, q, a, w0, w1}, .k1 = k1, .k2 = k2, .sn = sn};
+    const FdStepNoise nz = {seed, sample_offset, per, draw};
+    return fd_step_run("fd_cfg_multistep_noise_step_f32", FD_STEP_MULTISTEP, s, stream, FD_NOISE_ALWAYS, &nz);
 }
 
 // ---- the composite forms ---------------------------------------------------------------------------------------------
@@ -448,23 +450,11 @@ extern "C" int fd_composite_ddim_step_f32(float* x, const float* eps_nhwc, const
     FD_PLAN(fd_composite_ddim_step_f32(x, eps_nhwc, weights, n_entities, eps_out, z0, noise, mask, B, C, HW, ld, cfg, guidance,
                                        c1, c2, c3, c4, v_prediction, k1, k2, sigma, seed, sample_offset, per, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    const char* const who = "fd_composite_ddim_step_f32";
-    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "%s: x or eps_nhwc is null", who);
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
-    const int rw = fd_composite_args(who, weights, n_entities);
-    if (rw != FD_OK) return rw;
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "%s: z0 / noise alias the latents", who);
-    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "%s: eps_out aliases the latents", who);
-    FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, cfg, v_prediction,
-                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
-    if (sigma != 0.f) {
-        const int rc = fd_noise_addr(who, seed, sample_offset, per, draw, 0, (unsigned long long)B * C * HW, &a.nz_addr);
-        if (rc != FD_OK) return rc;
-    }
-    a.wmap = weights;
-    a.n_ent = n_entities;
-    return fd_latent_step(FD_STEP_DDIM, a, stream);
+    FdStepArgs a = {.x = x, .eps = eps_nhwc, .eps_out = eps_out, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C, .HW = HW,
+                    .ld = ld, .cfg = cfg, .vpred = v_prediction, .g = guidance, .co = {c1, c2, c3, c4}, .k1 = k1, .k2 = k2,
+                    .sn = sigma, .wmap = weights, .n_ent = n_entities};
+    const FdStepNoise nz = {seed, sample_offset, per, draw};
+    return fd_step_run("fd_composite_ddim_step_f32", FD_STEP_DDIM, a, stream, 0, &nz);
 }
 
 extern "C" int fd_composite_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities,
@@ -475,9 +465,11 @@ extern "C" int fd_composite_multistep_step_f32(float* x, const float* eps_nhwc, 
     FD_PLAN(fd_composite_multistep_step_f32(x, eps_nhwc, weights, n_entities, m0_out, m1, z0, noise, mask, B, C, HW, ld, cfg,
                                             guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    return fd_multistep_noise_step("fd_composite_multistep_step_f32", x, eps_nhwc, weights, n_entities, m0_out, m1, z0, noise, mask,
-                                   B, C, HW, ld, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, per, draw,
-                                   stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C,
+                    .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .co = {p, q, a, w0, w1}, .k1 = k1, .k2 = k2, .sn = sn,
+                    .wmap = weights, .n_ent = n_entities};
+    const FdStepNoise nz = {seed, sample_offset, per, draw};
+    return fd_step_run("fd_composite_multistep_step_f32", FD_STEP_MULTISTEP, s, stream, FD_NOISE_ALWAYS, &nz);
 }
 
 extern "C" int fd_composite_linear_multistep_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities,
@@ -491,41 +483,15 @@ extern "C" int fd_composite_linear_multistep_step_f32(float* x, const float* eps
                                                    x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance, w0, w1, w2,
                                                    w3, a0, a1, a2, scale, k1, k2, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    return fd_linear_multistep_step("fd_composite_linear_multistep_step_f32", x, eps_nhwc, weights, n_entities, form, n_prev, h1,
-                                    h2, h3, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, mask, B, C, HW, ld, cfg, guidance,
-                                    w0, w1, w2, w3, a0, a1, a2, scale, k1, k2, stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = h_out, .m1 = n_prev >= 1 ? h1 : nullptr, .z0 = z0, .nz = noise, .mask = mask,
+                    .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .k1 = k1, .k2 = k2,
+                    .h2 = n_prev >= 2 ? h2 : nullptr, .h3 = n_prev >= 3 ? h3 : nullptr, .x_src = x_src, .x_keep = x_keep_out,
+                    .x_scaled = x_scaled_out, .form = form, .n_prev = n_prev, .lw = {w0, w1, w2, w3}, .la = {a0, a1, a2}, .ls = scale,
+                    .wmap = weights, .n_ent = n_entities};
+    return fd_step_run("fd_composite_linear_multistep_step_f32", FD_STEP_LINEAR, s, stream);
 }
 
-// ---- the rescaled forms ----------------------------------------------------------------------------------------------
-// k_latent_step's vector rule; one workgroup per sample
-static int fd_latent_step_rescale(int update, const FdStepArgs& a, float phi, float* scale_out, void* stream) {
-    uintptr_t bases = (uintptr_t)a.eps_out | (uintptr_t)a.m0_out | (uintptr_t)a.m1;
-    if (update != FD_STEP_NONE || a.mask) bases |= (uintptr_t)a.x;
-    if (a.mask) bases |= (uintptr_t)a.z0 | (uintptr_t)a.nz | (uintptr_t)a.mask;
-    const int noise = update != FD_STEP_NONE && a.sn != 0.f;
-    const int vec = a.HW % 4 == 0 && bases % 16 == 0 && (!noise || a.nz_addr.per % 4 == 0);
-    static void (*const kernels[2][2][3])(const FdStepArgs, float, float*) = {
-        {{k_latent_step_rescale<1, FD_STEP_NONE, false>, k_latent_step_rescale<1, FD_STEP_DDIM, false>,
-          k_latent_step_rescale<1, FD_STEP_MULTISTEP, false>},
-         {k_latent_step_rescale<4, FD_STEP_NONE, false>, k_latent_step_rescale<4, FD_STEP_DDIM, false>,
-          k_latent_step_rescale<4, FD_STEP_MULTISTEP, false>}},
-        {{nullptr, k_latent_step_rescale<1, FD_STEP_DDIM, true>, k_latent_step_rescale<1, FD_STEP_MULTISTEP, true>},
-         {nullptr, k_latent_step_rescale<4, FD_STEP_DDIM, true>, k_latent_step_rescale<4, FD_STEP_MULTISTEP, true>}}};
-    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(a.B), dim3(FD_RESCALE_THREADS), 0, (hipStream_t)stream, a, phi,
-                       scale_out);
-    FD_CHECK_LAUNCH("k_latent_step_rescale");
-    return FD_OK;
-}
-
-// the checks the two rescaled entry points share (the siblings' own, plus the factor's range and the sample size)
-static int fd_rescale_args(const char* who, const float* eps_nhwc, int B, int C, int HW, int ld, float rescale) {
-    FD_CHECK_ARG(eps_nhwc, FD_EINVAL, "%s: eps_nhwc is null", who);
-    FD_CHECK_ARG(B > 0 && C > 0 && HW > 0 && ld >= C, FD_EINVAL, "%s: sizes", who);
-    FD_CHECK_ARG((unsigned long long)C * HW <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * HW past 2^31", who);
-    FD_CHECK_ARG(rescale >= 0.f && rescale <= 1.f, FD_EINVAL, "%s: rescale %g is outside [0, 1]", who, (double)rescale);
-    return FD_OK;
-}
-
+// ---- the rescaled forms: CFG is on, a sample of the noise is the C HW elements its statistics run over ------------------
 extern "C" int fd_cfg_rescale_ddim_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* scale_out,
                                             const float* z0, const float* noise, const float* mask, int B, int C, int HW,
                                             int ld, float guidance, float rescale, float c1, float c2, float c3, float c4,
@@ -535,22 +501,12 @@ extern "C" int fd_cfg_rescale_ddim_step_f32(float* x, const float* eps_nhwc, flo
                                          c1, c2, c3, c4, v_prediction, do_step, k1, k2, sigma, seed, sample_offset, draw,
                                          fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    const int rc = fd_rescale_args("fd_cfg_rescale_ddim_step_f32", eps_nhwc, B, C, HW, ld, rescale);
-    if (rc != FD_OK) return rc;
-    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: x is null");
-    FD_CHECK_ARG(do_step || (eps_out && !mask && sigma == 0.f), FD_EINVAL,
-                 "fd_cfg_rescale_ddim_step_f32: the combine-only form needs eps_out and takes neither mask nor sigma");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: z0 / noise alias the latents");
-    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "fd_cfg_rescale_ddim_step_f32: eps_out aliases the latents");
-    FdStepArgs a = {x, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, HW, ld, 1, v_prediction,
-                    guidance, {c1, c2, c3, c4, 0.f}, k1, k2, do_step ? sigma : 0.f, {}};
-    if (a.sn != 0.f) {
-        const int rn = fd_noise_addr("fd_cfg_rescale_ddim_step_f32", seed, sample_offset, C * HW, draw, 0,
-                                     (unsigned long long)B * C * HW, &a.nz_addr);
-        if (rn != FD_OK) return rn;
-    }
-    return fd_latent_step_rescale(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, rescale, scale_out, stream);
+    FdStepArgs a = {.x = x, .eps = eps_nhwc, .eps_out = eps_out, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C, .HW = HW,
+                    .ld = ld, .cfg = 1, .vpred = v_prediction, .g = guidance, .co = {c1, c2, c3, c4}, .k1 = k1, .k2 = k2,
+                    .sn = sigma};                                    // (the combine-only form, do_step == 0, takes no sigma)
+    const FdStepNoise nz = {seed, sample_offset, 0, draw};
+    const FdStepRescale rs = {rescale, scale_out};
+    return fd_step_run("fd_cfg_rescale_ddim_step_f32", do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream, 0, &nz, &rs);
 }
 
 extern "C" int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc, float* m0_out, const float* m1,
@@ -561,20 +517,11 @@ extern "C" int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc
     FD_PLAN(fd_cfg_rescale_multistep_step_f32(x, eps_nhwc, m0_out, m1, scale_out, z0, noise, mask, B, C, HW, ld, guidance,
                                               rescale, p, q, a, w0, w1, k1, k2, sn, seed, sample_offset, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    const int rc = fd_rescale_args("fd_cfg_rescale_multistep_step_f32", eps_nhwc, B, C, HW, ld, rescale);
-    if (rc != FD_OK) return rc;
-    FD_CHECK_ARG(x && m0_out, FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: x or m0_out is null");
-    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: m0_out aliases the latents or m1");
-    FD_CHECK_ARG(!mask || (z0 && noise), FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: mask without z0 / noise (null)");
-    FD_CHECK_ARG(!mask || (x != z0 && x != noise), FD_EINVAL, "fd_cfg_rescale_multistep_step_f32: z0 / noise alias the latents");
-    FdStepArgs s = {x, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, HW, ld, 1, 0,
-                    guidance, {p, q, a, w0, w1}, k1, k2, sn, {}};
-    if (sn != 0.f) {
-        const int rn = fd_noise_addr("fd_cfg_rescale_multistep_step_f32", seed, sample_offset, C * HW, draw, 0,
-                                     (unsigned long long)B * C * HW, &s.nz_addr);
-        if (rn != FD_OK) return rn;
-    }
-    return fd_latent_step_rescale(FD_STEP_MULTISTEP, s, rescale, scale_out, stream);
+    FdStepArgs s = {.x = x, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise, .mask = mask, .B = B, .C = C,
+                    .HW = HW, .ld = ld, .cfg = 1, .g = guidance, .co = {p, q, a, w0, w1}, .k1 = k1, .k2 = k2, .sn = sn};
+    const FdStepNoise nz = {seed, sample_offset, 0, draw};
+    const FdStepRescale rs = {rescale, scale_out};
+    return fd_step_run("fd_cfg_rescale_multistep_step_f32", FD_STEP_MULTISTEP, s, stream, 0, &nz, &rs);
 }
 
 // One thread owns one Philox block: elements 4q..4q+3 of one sample, as far as the sample and the buffer reach.

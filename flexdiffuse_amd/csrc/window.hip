@@ -18,6 +18,7 @@
 // fd_cfg_ddim_step_f32 (the other two fronts: to fd_cfg_ddim_noise_step_f32 / fd_cfg_multistep_[noise_]step_f32).
 #include "latent_step.h"
 #include "philox.h"
+#include "step_args.h"
 #include "window_grid.h"
 
 enum { FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
@@ -164,10 +165,40 @@ extern "C" int fd_window_gather_f32(const float* canvas, float* windows, int B, 
     return FD_OK;
 }
 
-// V = 4 when the eps rows can be read as float4 along the channels, else V = 1; grid; launch.  sn == 0 launches the kernels
-// without the noise stage.
-static int fd_window_step_launch(int update, const FdWindowStepArgs& a, void* stream) {
+// ---- the host path of the three step fronts: each names the fields it sets; fd_window_step_run checks, selects, launches -------
+// the checks of the three fronts: required pointers, the combine-only form, grid, sizes, blend, the known-region blend and
+// every alias a launch could trip over (windows_out is written while every other buffer of the call is still being read)
+static int fd_window_front_args(const char* who, int update, const FdWindowStepArgs& a) {
+    FD_CHECK_ARG(a.eps, FD_EINVAL, "%s: eps_nhwc is null", who);
+    FD_CHECK_ARG(a.x || update == FD_STEP_NONE, FD_EINVAL, "%s: x is null", who);
+    FD_CHECK_ARG(a.m0_out || update != FD_STEP_MULTISTEP, FD_EINVAL, "%s: m0_out is null", who);
+    FD_CHECK_ARG(update != FD_STEP_NONE || (a.eps_out && !a.wout), FD_EINVAL,
+                 "%s: the combine-only form needs eps_out (null) and writes no windows", who);
+    FD_TRY(fd_window_grid_args(who, a.B, a.C, a.g));
+    FD_CHECK_ARG(a.ld >= a.C, FD_EINVAL, "%s: sizes: ld %d < C %d", who, a.ld, a.C);
+    FD_CHECK_ARG(a.tent == FD_BLEND_UNIFORM || a.tent == FD_BLEND_TENT, FD_EINVAL,
+                 "%s: blend %d is neither uniform (0) nor tent (1)", who, a.tent);
+    FD_TRY(fd_blend_args(who, a.x, a.z0, a.nz, a.mask, "canvas"));
+    FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x, FD_EINVAL, "%s: eps_out aliases the canvas", who);
+    FD_CHECK_ARG(!a.m0_out || (a.m0_out != a.x && a.m0_out != a.m1), FD_EINVAL, "%s: m0_out aliases the canvas or m1", who);
+    const void* others[] = {a.x, a.eps, a.eps_out, a.m0_out, a.m1, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr, a.mask};
+    for (const void* o : others)
+        FD_CHECK_ARG(!a.wout || a.wout != o, FD_EINVAL, "%s: windows_out aliases another buffer of the call", who);
+    return FD_OK;
+}
+
+// The checks; the noise address (sn != 0: per = C H W, the launch's first sample at sample_offset, stream 0); V = 4 when the eps
+// rows can be read as float4 along the channels, else V = 1; grid; launch.  sn == 0 launches the kernels without the noise
+// stage; the noise stage needs an update (`noise` below), so the table's holes are never read.
+static int fd_window_step_run(const char* who, int update, FdWindowStepArgs& a, uint64_t seed, int64_t sample_offset, int draw,
+                              void* stream) {
+    FD_TRY(fd_window_front_args(who, update, a));
     const int noise = update != FD_STEP_NONE && a.sn != 0.f;
+    if (noise) {
+        const unsigned long long per = (unsigned long long)a.C * a.g.H * a.g.W;
+        FD_CHECK_ARG(per <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * H * W past 2^31", who);
+        FD_TRY(fd_noise_addr(who, seed, sample_offset, (int)per, draw, 0, per * a.B, &a.nz_addr));
+    }
     const int vec = a.C % 4 == 0 && a.ld % 4 == 0 && (uintptr_t)a.eps % 16 == 0;
     static void (*const kernels[2][2][3])(const FdWindowStepArgs) = {
         {{k_window_step<1, FD_STEP_NONE, false>, k_window_step<1, FD_STEP_DDIM, false>, k_window_step<1, FD_STEP_MULTISTEP, false>},
@@ -187,46 +218,10 @@ extern "C" int fd_window_step_f32(float* x, float* windows_out, const float* eps
     FD_PLAN(fd_window_step_f32(x, windows_out, eps_nhwc, eps_out, B, C, ld, H, W, h, w, stride_y, stride_x, ny, nx, blend,
                                cfg, guidance, c1, c2, c3, c4, v_prediction, do_step, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(eps_nhwc, FD_EINVAL, "fd_window_step_f32: eps_nhwc is null");
-    FD_CHECK_ARG(!do_step || x, FD_EINVAL, "fd_window_step_f32: x is null");
-    FD_CHECK_ARG(do_step || (eps_out && !windows_out), FD_EINVAL,
-                 "fd_window_step_f32: the combine-only form needs eps_out (null) and writes no windows");
-    const FdWindowGrid g = {H, W, h, w, stride_y, stride_x, ny, nx};
-    const int rc = fd_window_grid_args("fd_window_step_f32", B, C, g);
-    if (rc != FD_OK) return rc;
-    FD_CHECK_ARG(ld >= C, FD_EINVAL, "fd_window_step_f32: sizes: ld %d < C %d", ld, C);
-    FD_CHECK_ARG(blend == FD_BLEND_UNIFORM || blend == FD_BLEND_TENT, FD_EINVAL,
-                 "fd_window_step_f32: blend %d is neither uniform (0) nor tent (1)", blend);
-    FD_CHECK_ARG(!eps_out || eps_out != x, FD_EINVAL, "fd_window_step_f32: eps_out aliases the canvas");
-    FD_CHECK_ARG(!windows_out || (windows_out != x && windows_out != eps_out), FD_EINVAL,
-                 "fd_window_step_f32: windows_out aliases the canvas or eps_out");
-    const FdWindowStepArgs a = {x, windows_out, eps_nhwc, eps_out, nullptr, nullptr, nullptr, nullptr, nullptr, B, C, ld, blend,
-                                cfg ? 1 : 0, v_prediction, g, guidance, {c1, c2, c3, c4, 0.f}, 1.f, 0.f, 0.f, {}};
-    return fd_window_step_launch(do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, stream);
-}
-
-// the checks the DDIM and multistep fronts share after their own null checks: grid, sizes, blend, the known-region blend
-// and every alias a launch could trip over (windows_out is written while the canvas-shaped buffers are still being read)
-static int fd_window_front_args(const char* who, const FdWindowStepArgs& a) {
-    const int rc = fd_window_grid_args(who, a.B, a.C, a.g);
-    if (rc != FD_OK) return rc;
-    FD_CHECK_ARG(a.ld >= a.C, FD_EINVAL, "%s: sizes: ld %d < C %d", who, a.ld, a.C);
-    FD_CHECK_ARG(a.tent == FD_BLEND_UNIFORM || a.tent == FD_BLEND_TENT, FD_EINVAL,
-                 "%s: blend %d is neither uniform (0) nor tent (1)", who, a.tent);
-    FD_CHECK_ARG(!a.mask || (a.z0 && a.nz), FD_EINVAL, "%s: mask without z0 / noise (null)", who);
-    FD_CHECK_ARG(!a.mask || (a.x != a.z0 && a.x != a.nz), FD_EINVAL, "%s: z0 / noise alias the canvas", who);
-    FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x, FD_EINVAL, "%s: eps_out aliases the canvas", who);
-    const void* others[] = {a.x, a.eps, a.eps_out, a.m0_out, a.m1, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr, a.mask};
-    for (const void* o : others)
-        FD_CHECK_ARG(!a.wout || a.wout != o, FD_EINVAL, "%s: windows_out aliases another buffer of the call", who);
-    return FD_OK;
-}
-
-// the noise address of a front: per = C H W, the launch's first sample at sample_offset, stream 0
-static int fd_window_noise(const char* who, FdWindowStepArgs& a, uint64_t seed, int64_t sample_offset, int draw) {
-    const unsigned long long per = (unsigned long long)a.C * a.g.H * a.g.W;
-    FD_CHECK_ARG(per <= 0x7fffffffull, FD_EINVAL, "%s: sizes: C * H * W past 2^31", who);
-    return fd_noise_addr(who, seed, sample_offset, (int)per, draw, 0, per * a.B, &a.nz_addr);
+    FdWindowStepArgs a = {.x = x, .wout = windows_out, .eps = eps_nhwc, .eps_out = eps_out, .B = B, .C = C, .ld = ld, .tent = blend,
+                          .cfg = cfg ? 1 : 0, .vpred = v_prediction, .g = {H, W, h, w, stride_y, stride_x, ny, nx},
+                          .gscale = guidance, .co = {c1, c2, c3, c4}};
+    return fd_window_step_run("fd_window_step_f32", do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, 0, 0, 0, stream);
 }
 
 extern "C" int fd_window_ddim_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, const float* z0,
@@ -238,14 +233,11 @@ extern "C" int fd_window_ddim_step_f32(float* x, float* windows_out, const float
                                     stride_x, ny, nx, blend, cfg, guidance, c1, c2, c3, c4, v_prediction, k1, k2, sigma, seed,
                                     sample_offset, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc, FD_EINVAL, "fd_window_ddim_step_f32: x or eps_nhwc is null");
-    FdWindowStepArgs a = {x, windows_out, eps_nhwc, eps_out, nullptr, nullptr, z0, noise, mask, B, C, ld, blend,
-                          cfg ? 1 : 0, v_prediction, {H, W, h, w, stride_y, stride_x, ny, nx}, guidance,
-                          {c1, c2, c3, c4, 0.f}, k1, k2, sigma, {}};
-    int rc = fd_window_front_args("fd_window_ddim_step_f32", a);
-    if (rc != FD_OK) return rc;
-    if (sigma != 0.f && (rc = fd_window_noise("fd_window_ddim_step_f32", a, seed, sample_offset, draw)) != FD_OK) return rc;
-    return fd_window_step_launch(FD_STEP_DDIM, a, stream);
+    FdWindowStepArgs a = {.x = x, .wout = windows_out, .eps = eps_nhwc, .eps_out = eps_out, .z0 = z0, .nz = noise, .mask = mask,
+                          .B = B, .C = C, .ld = ld, .tent = blend, .cfg = cfg ? 1 : 0, .vpred = v_prediction,
+                          .g = {H, W, h, w, stride_y, stride_x, ny, nx}, .gscale = guidance, .co = {c1, c2, c3, c4}, .k1 = k1,
+                          .k2 = k2, .sn = sigma};
+    return fd_window_step_run("fd_window_ddim_step_f32", FD_STEP_DDIM, a, seed, sample_offset, draw, stream);
 }
 
 extern "C" int fd_window_multistep_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* m0_out,
@@ -258,13 +250,9 @@ extern "C" int fd_window_multistep_step_f32(float* x, float* windows_out, const 
                                          stride_x, ny, nx, blend, cfg, guidance, p, q, a, w0, w1, k1, k2, sn, seed,
                                          sample_offset, draw, fd_s_));
     FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
-    FD_CHECK_ARG(x && eps_nhwc && m0_out, FD_EINVAL, "fd_window_multistep_step_f32: x, eps_nhwc or m0_out is null");
-    FD_CHECK_ARG(m0_out != x && m0_out != m1, FD_EINVAL, "fd_window_multistep_step_f32: m0_out aliases the canvas or m1");
-    FdWindowStepArgs s = {x, windows_out, eps_nhwc, nullptr, m0_out, m1, z0, noise, mask, B, C, ld, blend,
-                          cfg ? 1 : 0, 0, {H, W, h, w, stride_y, stride_x, ny, nx}, guidance,
-                          {p, q, a, w0, w1}, k1, k2, sn, {}};
-    int rc = fd_window_front_args("fd_window_multistep_step_f32", s);
-    if (rc != FD_OK) return rc;
-    if (sn != 0.f && (rc = fd_window_noise("fd_window_multistep_step_f32", s, seed, sample_offset, draw)) != FD_OK) return rc;
-    return fd_window_step_launch(FD_STEP_MULTISTEP, s, stream);
+    FdWindowStepArgs s = {.x = x, .wout = windows_out, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise,
+                          .mask = mask, .B = B, .C = C, .ld = ld, .tent = blend, .cfg = cfg ? 1 : 0,
+                          .g = {H, W, h, w, stride_y, stride_x, ny, nx}, .gscale = guidance, .co = {p, q, a, w0, w1}, .k1 = k1,
+                          .k2 = k2, .sn = sn};
+    return fd_window_step_run("fd_window_multistep_step_f32", FD_STEP_MULTISTEP, s, seed, sample_offset, draw, stream);
 }

@@ -1083,16 +1083,46 @@ def _check_eps_rows(eps_nhwc: torch.Tensor, rows: int, C: int):
     assert eps_nhwc.shape[0] >= rows and eps_nhwc.shape[1] >= C, (tuple(eps_nhwc.shape), rows, C)
 
 
+# ---- the step wrappers: what they share, once ---------------------------------------------------------------------------------
+def _blend(mask, cells: int, numel: int):
+    '''mask = (z0, noise, mask [cells], k1, k2) of the known-region blend, or None: checked, as (z0, noise, mask, k1, k2).'''
+    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
+    _check_f32(numel, z0, nz)
+    _check_f32(cells, mk)
+    return z0, nz, mk, float(k1), float(k2)
+
+
+def _noise_address(noise, coefficient: float):
+    '''(seed, sample_offset) of `noise`, a `PhiloxNoise`; None: (0, 0), which goes with a zero noise coefficient only.'''
+    assert not coefficient or noise is not None, 'a noise coefficient without a PhiloxNoise'
+    return (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
+
+
+def _floats(values, n: int):
+    '''The first n of `values` as floats, padded with zeros.'''
+    out = [float(v) for v in values][:n]
+    return out + [0.0] * (n - len(out))
+
+
+def _guided_rows(eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, HW: int, cfg: bool):
+    '''eps_nhwc holds at least (cfg + 1 + n) B HW rows, n the entities of `weights`, fp32 [n][HW] (None or n == 0: none).
+    Returns the (weights, n) a composite front hands the library.'''
+    n = 0 if weights is None else int(weights.shape[0])
+    if n:
+        _check_f32(n * HW, weights)
+    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * HW, C)
+    return (_p(weights) if n else None), n
+
+
 def cfg_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, HW: int,
                   cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                   do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
     '''CFG combine of eps_nhwc (-> eps_out, NCHW fp32, when given) and, with do_step, the DDIM update of x (NCHW fp32, in
     place): fd_cfg_ddim_step_f32.'''
     _check_f32(B * C * HW, x, eps_out)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
-    hip.call('fd_cfg_ddim_step_f32', _p(x), eps_nhwc.data_ptr(), _p(eps_out), B, C, HW,
-             eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]),
-             float(coef[2]), float(coef[3]), int(v_prediction), int(do_step), hip.stream())
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    hip.call('fd_cfg_ddim_step_f32', _p(x), eps_nhwc.data_ptr(), _p(eps_out), B, C, HW, eps_nhwc.stride(0), int(cfg),
+             float(guidance), *_floats(coef, 4), int(v_prediction), int(do_step), hip.stream())
 
 
 def cfg_ddim_masked_step(x: torch.Tensor, eps_nhwc: Optional[torch.Tensor], z0: torch.Tensor, noise: torch.Tensor,
@@ -1105,11 +1135,19 @@ def cfg_ddim_masked_step(x: torch.Tensor, eps_nhwc: Optional[torch.Tensor], z0: 
     _check_f32(HW, mask)
     ld = 0
     if eps_nhwc is not None:
-        _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
+        _guided_rows(eps_nhwc, None, B, C, HW, cfg)
         ld = eps_nhwc.stride(0)
     hip.call('fd_cfg_ddim_masked_step_f32', x.data_ptr(), _p(eps_nhwc), z0.data_ptr(), noise.data_ptr(), mask.data_ptr(),
-             B, C, HW, ld, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
-             int(v_prediction), float(k1), float(k2), hip.stream())
+             B, C, HW, ld, int(cfg), float(guidance), *_floats(coef, 4), int(v_prediction), float(k1), float(k2), hip.stream())
+
+
+def _multistep_step(entry: str, x, eps_nhwc, entities, m0_out, m1, B, C, HW, cfg, guidance, coef, mask, noise_tail):
+    '''The body of the DPM-Solver++ fronts: `entities` the (weights, n) of a composite front, `noise_tail` the noise coefficient
+    and address of a stochastic one (each () where the entry point takes none).'''
+    z0, nz, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    _check_f32(B * C * HW, x, m0_out, m1)
+    hip.call(entry, x.data_ptr(), eps_nhwc.data_ptr(), *entities, m0_out.data_ptr(), _p(m1), _p(z0), _p(nz), _p(mk), B, C, HW,
+             eps_nhwc.stride(0), int(cfg), float(guidance), *_floats(coef, 5), k1, k2, *noise_tail, hip.stream())
 
 
 def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor], B: int,
@@ -1117,13 +1155,20 @@ def cfg_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Te
     '''DPM-Solver++ step (fd_cfg_multistep_step_f32), in place on x (NCHW fp32): e = CFG(eps_nhwc); m0 = p x + q e -> m0_out;
     x' = a x + w0 m0 (+ w1 m1 when m1 is given), coef = (p, q, a, w0, w1); with mask = (z0, noise, mask [HW], k1, k2) the
     known-region blend of `cfg_ddim_masked_step` on x'.'''
-    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * HW, x, m0_out, m1, z0, noise)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
-    hip.call('fd_cfg_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(z0), _p(noise),
-             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
-             float(coef[3]), float(coef[4]), float(k1), float(k2), hip.stream())
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    _multistep_step('fd_cfg_multistep_step_f32', x, eps_nhwc, (), m0_out, m1, B, C, HW, cfg, guidance, coef, mask, ())
+
+
+def _linear_multistep_step(entry: str, x, eps_nhwc, entities, form, hist, h_out, B, C, HW, cfg, guidance, weights, coef, mask,
+                           x_keep_out, x_src, x_scaled_out, scale):
+    '''The body of the PLMS / K-LMS fronts; `entities`: the (weights, n) of the composite front, () of the other.'''
+    z0, noise, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    hist = list(hist)
+    assert len(hist) <= 3 and len(weights) <= 4 and len(coef) == (3 if form else 2), (len(hist), len(weights), len(coef))
+    _check_f32(B * C * HW, x, h_out, x_keep_out, x_src, x_scaled_out, *hist)
+    hip.call(entry, x.data_ptr(), eps_nhwc.data_ptr(), *entities, int(form), len(hist), *([_p(t) for t in hist] + [None] * 3)[:3],
+             _p(h_out), _p(x_keep_out), _p(x_src), _p(x_scaled_out), _p(z0), _p(noise), _p(mk), B, C, HW, eps_nhwc.stride(0),
+             int(cfg), float(guidance), *_floats(weights, 4), *_floats(coef, 3), float(scale), k1, k2, hip.stream())
 
 
 def cfg_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, form: int, hist, h_out: Optional[torch.Tensor], B: int,
@@ -1135,19 +1180,9 @@ def cfg_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, form: int
     given); E = e | w0 e + w1 h1 (+ wk hk); x' = cs xs + ce E, xs = x_src when given, else x; weights = (w0, ...), coef = (cs, ce).
     Form 1: d = the derivative at coef = (-sigma, 1/sigma, -1/sigma) -> h_out; x' = x + c0 d (+ ck hk); weights = (c0, ...).
     Then the known-region blend of mask = (z0, noise, mask [HW], k1, k2), and scale x -> x_scaled_out when given.'''
-    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    hist = list(hist)
-    assert len(hist) <= 3 and len(weights) <= 4 and len(coef) == (3 if form else 2), (len(hist), len(weights), len(coef))
-    _check_f32(B * C * HW, x, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, *hist)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
-    h = [_p(t) for t in hist] + [None] * (3 - len(hist))
-    w = [float(v) for v in weights] + [0.0] * (4 - len(weights))
-    a = [float(v) for v in coef] + [0.0] * (3 - len(coef))
-    hip.call('fd_cfg_linear_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), int(form), len(hist), h[0], h[1], h[2],
-             _p(h_out), _p(x_keep_out), _p(x_src), _p(x_scaled_out), _p(z0), _p(noise), _p(mk), B, C, HW, eps_nhwc.stride(0),
-             int(cfg), float(guidance), w[0], w[1], w[2], w[3], a[0], a[1], a[2], float(scale), float(k1), float(k2),
-             hip.stream())
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    _linear_multistep_step('fd_cfg_linear_multistep_step_f32', x, eps_nhwc, (), form, hist, h_out, B, C, HW, cfg, guidance, weights,
+                           coef, mask, x_keep_out, x_src, x_scaled_out, scale)
 
 
 def philox_normal(out: torch.Tensor, per: int, seed: int, sample_offset: int = 0, draw: int = 0, stream: int = 1) -> torch.Tensor:
@@ -1160,20 +1195,23 @@ def philox_normal(out: torch.Tensor, per: int, seed: int, sample_offset: int = 0
     return out
 
 
+def _ddim_noise_step(entry: str, x, eps_nhwc, head, B, C, HW, cfg, guidance, coef, v_prediction, mask, noise_tail):
+    '''The body of the stochastic DDIM fronts: `head` the (weights, n, eps_out) of the composite front, () of the other.'''
+    z0, nz, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    _check_f32(B * C * HW, x)
+    hip.call(entry, x.data_ptr(), eps_nhwc.data_ptr(), *head, _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg),
+             float(guidance), *_floats(coef, 4), int(v_prediction), k1, k2, *noise_tail, hip.stream())
+
+
 def cfg_ddim_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, B: int, C: int, HW: int, cfg: bool, guidance: float, coef,
                         v_prediction: bool, sigma: float, noise, per: int, draw: int, mask=None):
     '''Stochastic DDIM step (fd_cfg_ddim_noise_step_f32), in place on x (NCHW fp32): the CFG + DDIM update of `cfg_ddim_step`
     with coef = (c1, c2, c3, c4) of `step_coefficients(t, eta)`, then x' += sigma z with z the stream of `noise` (a
     `PhiloxNoise`) at (`per` elements per sample, `draw`), generated in the kernel; with mask = (z0, noise, mask [HW], k1, k2)
     the known-region blend of `cfg_ddim_masked_step` on the result.  sigma == 0: the bits of those two.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * HW, x, z0, nz)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
-    hip.call('fd_cfg_ddim_noise_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(z0), _p(nz), _p(mk), B, C, HW,
-             eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]),
-             int(v_prediction), float(k1), float(k2), float(sigma), noise.seed, noise.sample_offset, int(per), int(draw),
-             hip.stream())
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    _ddim_noise_step('fd_cfg_ddim_noise_step_f32', x, eps_nhwc, (), B, C, HW, cfg, guidance, coef, v_prediction, mask,
+                     (float(sigma), noise.seed, noise.sample_offset, int(per), int(draw)))
 
 
 def cfg_multistep_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor],
@@ -1181,14 +1219,9 @@ def cfg_multistep_noise_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: to
                              draw: int, mask=None):
     '''SDE-DPM-Solver++ step (fd_cfg_multistep_noise_step_f32): `cfg_multistep_step` with x' += sn z after the update, z as
     in `cfg_ddim_noise_step`.  sn == 0: the bits of `cfg_multistep_step`.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * HW, C)
-    hip.call('fd_cfg_multistep_noise_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(z0), _p(nz),
-             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
-             float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn), noise.seed, noise.sample_offset, int(per),
-             int(draw), hip.stream())
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    _multistep_step('fd_cfg_multistep_noise_step_f32', x, eps_nhwc, (), m0_out, m1, B, C, HW, cfg, guidance, coef, mask,
+                    (float(sn), noise.seed, noise.sample_offset, int(per), int(draw)))
 
 
 def _check_scale_out(scale_out: Optional[torch.Tensor], B: int, like: torch.Tensor):
@@ -1205,17 +1238,13 @@ def cfg_rescale_ddim_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: 
     fp32 [B], when given) before eps_out and the update; with mask = (z0, noise, mask [HW], k1, k2) the known-region blend of
     `cfg_ddim_masked_step`; with sigma != 0 the step noise of `cfg_ddim_noise_step` from `noise` (a `PhiloxNoise`) at `draw`,
     C * HW elements per sample.  do_step False: the combine alone into eps_out.  rescale == 0: the bits of the siblings.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * HW, x, eps_out, z0, nz)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, 2 * B * HW, C)
+    z0, nz, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    _check_f32(B * C * HW, x, eps_out)
+    _guided_rows(eps_nhwc, None, B, C, HW, True)
     _check_scale_out(scale_out, B, eps_nhwc)
-    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
-    assert not sigma or noise is not None, 'sigma without a PhiloxNoise'
     hip.call('fd_cfg_rescale_ddim_step_f32', _p(x), eps_nhwc.data_ptr(), _p(eps_out), _p(scale_out), _p(z0), _p(nz), _p(mk),
-             B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), float(coef[0]), float(coef[1]), float(coef[2]),
-             float(coef[3]), int(v_prediction), int(do_step), float(k1), float(k2), float(sigma), seed, offset, int(draw),
-             hip.stream())
+             B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), *_floats(coef, 4), int(v_prediction), int(do_step),
+             k1, k2, float(sigma), *_noise_address(noise, sigma), int(draw), hip.stream())
 
 
 def cfg_rescale_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: torch.Tensor, m1: Optional[torch.Tensor],
@@ -1224,17 +1253,13 @@ def cfg_rescale_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m0_out: 
     '''CFG + guidance rescale + DPM-Solver++ step (fd_cfg_rescale_multistep_step_f32): `cfg_multistep_step` (sn != 0:
     `cfg_multistep_noise_step`, C * HW elements per sample) with CFG on and the guided output rescaled as in
     `cfg_rescale_ddim_step`.  rescale == 0: the bits of those two.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
-    _check_f32(HW, mk)
-    _check_eps_rows(eps_nhwc, 2 * B * HW, C)
+    z0, nz, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    _check_f32(B * C * HW, x, m0_out, m1)
+    _guided_rows(eps_nhwc, None, B, C, HW, True)
     _check_scale_out(scale_out, B, eps_nhwc)
-    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
-    assert not sn or noise is not None, 'sn without a PhiloxNoise'
     hip.call('fd_cfg_rescale_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1), _p(scale_out),
-             _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), float(coef[0]),
-             float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn), seed, offset,
-             int(draw), hip.stream())
+             _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), float(guidance), float(rescale), *_floats(coef, 5), k1, k2,
+             float(sn), *_noise_address(noise, sn), int(draw), hip.stream())
 
 
 def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int,
@@ -1242,23 +1267,11 @@ def composite_step(x: Optional[torch.Tensor], eps_nhwc: torch.Tensor, weights: O
                    do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
     '''CompositeGuide step (fd_composite_step_f32): eps_nhwc [(cfg + 1 + n) * B * HW][ld] fp32 in rep-major order,
     weights [n][HW] fp32 (None: no entity) -> blend, CFG, optionally the DDIM update of x (NCHW fp32, in place).'''
-    n = 0 if weights is None else weights.shape[0]
-    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * HW, C)
+    n = _guided_rows(eps_nhwc, weights, B, C, HW, cfg)[1]
     _check_f32(n * HW, weights)
     _check_f32(B * C * HW, x, eps_out)
     hip.call('fd_composite_step_f32', _p(x), eps_nhwc.data_ptr(), _p(weights), _p(eps_out), B, C, HW,
-             eps_nhwc.stride(0), n, int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
-             float(coef[3]), int(v_prediction), int(do_step), hip.stream())
-
-
-def _composite_rows(eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, HW: int, cfg: bool) -> int:
-    '''The checks the composite step fronts share: weights fp32 [n][HW] (None or n == 0: no entity), eps_nhwc at least
-    (cfg + 1 + n) B HW rows.  Returns n.'''
-    n = 0 if weights is None else int(weights.shape[0])
-    if n:
-        _check_f32(n * HW, weights)
-    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * HW, C)
-    return n
+             eps_nhwc.stride(0), n, int(cfg), float(guidance), *_floats(coef, 4), int(v_prediction), int(do_step), hip.stream())
 
 
 def composite_ddim_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, HW: int,
@@ -1268,16 +1281,10 @@ def composite_ddim_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Option
     eps_nhwc [(cfg + 1 + n) * B * HW][ld] (-> eps_out when given), the DDIM update, x' += sigma z (sigma != 0: z the stream of
     `noise`, a `PhiloxNoise`, at `per` elements per sample and `draw`) and, with mask = (z0, noise, mask [HW], k1, k2), the
     known-region blend of `cfg_ddim_masked_step` -- one launch.  Neither: the bits of `composite_step`.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    n = _composite_rows(eps_nhwc, weights, B, C, HW, cfg)
-    _check_f32(B * C * HW, x, eps_out, z0, nz)
-    _check_f32(HW, mk)
-    assert not sigma or noise is not None, 'sigma without a PhiloxNoise'
-    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
-    hip.call('fd_composite_ddim_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights) if n else None, n, _p(eps_out),
-             _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), float(coef[0]), float(coef[1]),
-             float(coef[2]), float(coef[3]), int(v_prediction), float(k1), float(k2), float(sigma), seed, offset,
-             int(per) if per else C * HW, int(draw), hip.stream())
+    _check_f32(B * C * HW, eps_out)
+    _ddim_noise_step('fd_composite_ddim_step_f32', x, eps_nhwc, (*_guided_rows(eps_nhwc, weights, B, C, HW, cfg), _p(eps_out)),
+                     B, C, HW, cfg, guidance, coef, v_prediction, mask,
+                     (float(sigma), *_noise_address(noise, sigma), int(per) if per else C * HW, int(draw)))
 
 
 def composite_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], m0_out: torch.Tensor,
@@ -1285,16 +1292,8 @@ def composite_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: O
                              sn: float = 0.0, noise=None, per: int = 0, draw: int = 0):
     '''CompositeGuide DPM-Solver++ step (fd_composite_multistep_step_f32): `cfg_multistep_step` (sn != 0:
     `cfg_multistep_noise_step`) on the blend + CFG of `composite_step`'s rows -- one launch.'''
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    n = _composite_rows(eps_nhwc, weights, B, C, HW, cfg)
-    _check_f32(B * C * HW, x, m0_out, m1, z0, nz)
-    _check_f32(HW, mk)
-    assert not sn or noise is not None, 'sn without a PhiloxNoise'
-    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
-    hip.call('fd_composite_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights) if n else None, n,
-             m0_out.data_ptr(), _p(m1), _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance),
-             float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), float(k1), float(k2), float(sn),
-             seed, offset, int(per) if per else C * HW, int(draw), hip.stream())
+    _multistep_step('fd_composite_multistep_step_f32', x, eps_nhwc, _guided_rows(eps_nhwc, weights, B, C, HW, cfg), m0_out, m1, B,
+                    C, HW, cfg, guidance, coef, mask, (float(sn), *_noise_address(noise, sn), int(per) if per else C * HW, int(draw)))
 
 
 def composite_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights_map: Optional[torch.Tensor], form: int,
@@ -1304,19 +1303,8 @@ def composite_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, wei
                                     scale: float = 0.0):
     '''CompositeGuide PLMS / K-LMS step (fd_composite_linear_multistep_step_f32): `cfg_linear_multistep_step`, argument for
     argument, on the blend + CFG of `composite_step`'s rows with the entity maps `weights_map` [n][HW] -- one launch.'''
-    z0, noise, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    hist = list(hist)
-    assert len(hist) <= 3 and len(weights) <= 4 and len(coef) == (3 if form else 2), (len(hist), len(weights), len(coef))
-    n = _composite_rows(eps_nhwc, weights_map, B, C, HW, cfg)
-    _check_f32(B * C * HW, x, h_out, x_keep_out, x_src, x_scaled_out, z0, noise, *hist)
-    _check_f32(HW, mk)
-    h = [_p(t) for t in hist] + [None] * (3 - len(hist))
-    w = [float(v) for v in weights] + [0.0] * (4 - len(weights))
-    a = [float(v) for v in coef] + [0.0] * (3 - len(coef))
-    hip.call('fd_composite_linear_multistep_step_f32', x.data_ptr(), eps_nhwc.data_ptr(), _p(weights_map) if n else None, n,
-             int(form), len(hist), h[0], h[1], h[2], _p(h_out), _p(x_keep_out), _p(x_src), _p(x_scaled_out), _p(z0), _p(noise),
-             _p(mk), B, C, HW, eps_nhwc.stride(0), int(cfg), float(guidance), w[0], w[1], w[2], w[3], a[0], a[1], a[2],
-             float(scale), float(k1), float(k2), hip.stream())
+    _linear_multistep_step('fd_composite_linear_multistep_step_f32', x, eps_nhwc, _guided_rows(eps_nhwc, weights_map, B, C, HW, cfg),
+                           form, hist, h_out, B, C, HW, cfg, guidance, weights, coef, mask, x_keep_out, x_src, x_scaled_out, scale)
 
 
 def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, grid):
@@ -1344,6 +1332,22 @@ def tile_blend(tiles: torch.Tensor, B: int, C: int, grid, feather, a: float = 1.
     return out
 
 
+def _window_step(entry: str, x, windows_out, eps_nhwc, outs, mask, B, C, grid, blend, cfg, guidance, coef, tail):
+    '''The body of the windowed fronts: `outs` the canvas-shaped buffers after eps_nhwc (None: an optional one left out),
+    `mask` the known-region blend of a front that takes one (False: it takes none), `coef` the floats after the guidance scale,
+    then (v_prediction,), k1 and k2 of the blend and `tail` up to the stream.'''
+    H, W, h, w, _, _, ny, nx = grid
+    blend_ptrs = blend_co = ()
+    if mask is not False:
+        z0, nz, mk, k1, k2 = _blend(mask, H * W, B * C * H * W)
+        blend_ptrs, blend_co = (_p(z0), _p(nz), _p(mk)), (k1, k2)
+    _check_f32(B * C * H * W, x, *outs)
+    _check_f32(B * ny * nx * C * h * w, windows_out)
+    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * ny * nx * h * w, C)
+    hip.call(entry, _p(x), _p(windows_out), eps_nhwc.data_ptr(), *(_p(t) for t in outs), *blend_ptrs, B, C, eps_nhwc.stride(0),
+             *(int(v) for v in grid), int(blend), int(cfg), float(guidance), *coef, *blend_co, *tail, hip.stream())
+
+
 def window_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, grid,
                 blend: int, cfg: bool, guidance: float, coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False,
                 do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
@@ -1351,27 +1355,8 @@ def window_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], 
     -> per canvas cell the CFG combine of every covering window, their average (blend 0: uniform, 1: tent) -> eps_out (NCHW
     fp32, optional), with do_step the DDIM update of the canvas x (NCHW fp32, in place) and, given windows_out
     (B Wn, C, h, w), the next step's window batch.'''
-    H, W, h, w, _, _, ny, nx = grid
-    _check_f32(B * C * H * W, x, eps_out)
-    _check_f32(B * ny * nx * C * h * w, windows_out)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * ny * nx * h * w, C)
-    hip.call('fd_window_step_f32', _p(x), _p(windows_out), eps_nhwc.data_ptr(), _p(eps_out), B, C, eps_nhwc.stride(0),
-             *(int(v) for v in grid), int(blend), int(cfg), float(guidance), float(coef[0]), float(coef[1]), float(coef[2]),
-             float(coef[3]), int(v_prediction), int(do_step), hip.stream())
-
-
-def _window_blend_noise(B: int, C: int, grid, x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor,
-                        cfg: bool, mask, sn: float, noise):
-    '''The checks the two windowed step fronts share; returns (z0, nz, mask, k1, k2, seed, sample_offset).'''
-    H, W, h, w, _, _, ny, nx = grid
-    z0, nz, mk, k1, k2 = mask if mask is not None else (None, None, None, 1.0, 0.0)
-    _check_f32(B * C * H * W, x, z0, nz)
-    _check_f32(H * W, mk)
-    _check_f32(B * ny * nx * C * h * w, windows_out)
-    _check_eps_rows(eps_nhwc, (2 if cfg else 1) * B * ny * nx * h * w, C)
-    assert not sn or noise is not None, 'a noise coefficient without a PhiloxNoise'
-    seed, offset = (noise.seed, noise.sample_offset) if noise is not None else (0, 0)
-    return z0, nz, mk, float(k1), float(k2), seed, offset
+    _window_step('fd_window_step_f32', x, windows_out, eps_nhwc, (eps_out,), False, B, C, grid, blend, cfg, guidance,
+                 (*_floats(coef, 4), int(v_prediction)), (int(do_step),))
 
 
 def window_ddim_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, B: int, C: int, grid,
@@ -1381,12 +1366,8 @@ def window_ddim_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_n
     stream of `noise`, a `PhiloxNoise`, at `draw`, addressed by the canvas element: C H W elements per sample) and, with
     mask = (z0, noise, mask [H W], k1, k2), the known-region blend of `cfg_ddim_masked_step` on the canvas; windows_out
     receives the blended canvas.  Neither: the bits of `window_step`.'''
-    z0, nz, mk, k1, k2, seed, offset = _window_blend_noise(B, C, grid, x, windows_out, eps_nhwc, cfg, mask, sigma, noise)
-    _check_f32(x.numel(), eps_out)
-    hip.call('fd_window_ddim_step_f32', x.data_ptr(), _p(windows_out), eps_nhwc.data_ptr(), _p(eps_out), _p(z0), _p(nz),
-             _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg), float(guidance), float(coef[0]),
-             float(coef[1]), float(coef[2]), float(coef[3]), int(v_prediction), k1, k2, float(sigma), seed, offset, int(draw),
-             hip.stream())
+    _window_step('fd_window_ddim_step_f32', x, windows_out, eps_nhwc, (eps_out,), mask, B, C, grid, blend, cfg, guidance,
+                 (*_floats(coef, 4), int(v_prediction)), (float(sigma), *_noise_address(noise, sigma), int(draw)))
 
 
 def window_multistep_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor, m0_out: torch.Tensor,
@@ -1396,12 +1377,9 @@ def window_multistep_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], 
     `window_step`; m0 = p x + q e -> m0_out; x' = a x + w0 m0 (+ w1 m1 when m1 is given), coef = (p, q, a, w0, w1); x' += sn z
     (sn != 0: the SDE form, z as in `window_ddim_step`); the blend of `mask`; windows_out (optional) <- the next window
     batch.  m0_out and m1 are canvas-shaped.'''
-    z0, nz, mk, k1, k2, seed, offset = _window_blend_noise(B, C, grid, x, windows_out, eps_nhwc, cfg, mask, sn, noise)
-    _check_f32(x.numel(), m0_out, m1)
-    hip.call('fd_window_multistep_step_f32', x.data_ptr(), _p(windows_out), eps_nhwc.data_ptr(), m0_out.data_ptr(), _p(m1),
-             _p(z0), _p(nz), _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg), float(guidance),
-             float(coef[0]), float(coef[1]), float(coef[2]), float(coef[3]), float(coef[4]), k1, k2, float(sn), seed, offset,
-             int(draw), hip.stream())
+    assert m0_out is not None
+    _window_step('fd_window_multistep_step_f32', x, windows_out, eps_nhwc, (m0_out, m1), mask, B, C, grid, blend, cfg, guidance,
+                 _floats(coef, 5), (float(sn), *_noise_address(noise, sn), int(draw)))
 
 
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
