@@ -14,6 +14,7 @@ preprocess = _encode.preprocess
 FlexPipeline = _flex.FlexPipeline
 
 from .pipeline.guide import GuideBase, PromptGuide, ScheduledGuide, SimpleGuide, WindowedGuide  # noqa: E402,F401
+from .composition.guide import CompositeGuide, WindowedCompositeGuide  # noqa: E402,F401
 from .noise import PhiloxNoise  # noqa: E402,F401
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler,  # noqa: E402,F401
                         LMSDiscreteScheduler, PNDMScheduler)

@@ -1,2 +1,2 @@
-from .guide import CompositeGuide  # noqa: F401
+from .guide import CompositeGuide, WindowedCompositeGuide  # noqa: F401
 from .schema import EntitySchema, Schema  # noqa: F401

@@ -30,8 +30,11 @@ import torch.nn.functional as F
 
 from .. import hip, ops
 from ..ctx_schedule import ContextSchedule, step_weights
-from ..pipeline.guide import GuideBase
+from ..pipeline.guide import GuideBase, WindowedGuide
 from .schema import EntitySchema, Schema
+
+
+MAX_WINDOW_ENTITIES = 16          # FD_WINDOW_MAX_ENTITIES, csrc/window.hip
 
 
 def px_to_block(px_shape: Sequence[int]) -> Tuple[int, ...]:
@@ -183,3 +186,89 @@ class CompositeGuide(GuideBase):
         ops.cfg_ddim_step(None, stack[:2].reshape(-1, 1), C, 1, H * W, True, self.guidance,
                           do_step=False, eps_out=out)
         return out
+
+
+class WindowedCompositeGuide(WindowedGuide):
+    '''CompositeGuide over a canvas larger than the model's own size (beyond the reference): region composition, the headline
+    use of MultiDiffusion (Bar-Tal et al. 2023), on `WindowedGuide`'s window batch.  Entities live on the CANVAS: `offset`,
+    `size` and `mask` of the schema's entities are in canvas pixels, `weights(H, W)` is `weight_maps` over the canvas
+    latent, and a cell's weight does not depend on the window grid.  The UNet batch is the window batch (B Wn latent rows)
+    under `rep` = E = cfg + 1 + n context blocks in rep-major order, [uncond] * (B Wn), [bg] * (B Wn), [e_1] * (B Wn) ...;
+    per covering window the entities are blended onto the background and CFG is applied, then the windows are averaged and
+    ONE step is taken on the canvas -- one launch after the UNet (fd_window_composite_step_f32,
+    fd_window_composite_multistep_step_f32).  Every (entity, window) pair is computed, also where the two do not intersect:
+    those rows meet weight 0.  `gather`, `bind`, `grid` and `noise_pred` are WindowedGuide's, so FlexPipeline routes this guide
+    as it routes that one; `guidance_rescale` and `style_linear` are refused.  A canvas equal to the window is CompositeGuide,
+    a schema without entities WindowedGuide on the background prompt, both bit for bit.'''
+
+    def __init__(self, encoder, unet, guidance: float, schema: Schema, steps: int, *, batch_size: int = 1, window=512,
+                 stride=256, blend: str = 'uniform', style_linear=None, guidance_rescale: float = 0.0):
+        if style_linear is not None:
+            raise ValueError('WindowedCompositeGuide does not support style_linear')
+        if guidance_rescale:
+            raise ValueError('WindowedCompositeGuide does not support guidance_rescale: the per-sample standard deviations '
+                             'would have to span the canvas')
+        if int(batch_size) < 1:
+            raise ValueError(f'batch_size must be >= 1, got {batch_size}')
+        B = int(batch_size)
+        self.schema = schema
+        self.background_embed = encoder.prompt(schema.background_prompt)
+        WindowedGuide.__init__(self, encoder, unet, guidance, steps, self.background_embed.expand(B, -1, -1), window=window,
+                               stride=stride, blend=blend)
+        self.entities: List[EntityEmbeds] = [
+            EntityEmbeds(encoder.prompt(e.prompt), px_to_block(e.offset), px_to_block(e.size),
+                         e.blend, getattr(e, 'mask', None)) for e in schema.entities]
+        if len(self.entities) > MAX_WINDOW_ENTITIES:
+            raise ValueError(f'{len(self.entities)} entities: at most {MAX_WINDOW_ENTITIES} over windows')
+        self._rows = [self.background_embed] + [e.embed for e in self.entities]
+        if self.classifier_free_guidance:
+            self._rows = [self.uncond_embeds] + self._rows
+        self._wmaps = {}
+
+    @property
+    def rep(self) -> int:
+        return len(self._rows)                   # E: context blocks of B Wn rows each
+
+    def stacked_embeds(self, count: Optional[int] = None) -> torch.Tensor:
+        '''The rep-major E * B * Wn context, built once per window count (default: the count of the last canvas bound).'''
+        count = self._count if count is None else count
+        if self._wstack is None or self._wstack[0] != count:
+            rows = self.batch_size * count
+            self._wstack = (count, None, torch.cat([r.float().expand(rows, -1, -1) for r in self._rows]).contiguous())
+        return self._wstack[2]
+
+    def weights(self, H: int, W: int) -> Optional[torch.Tensor]:
+        '''Device fp32 [n][H][W] blend weights over the canvas latent (None without entities), built once per canvas size and
+        kept: a captured graph / recorded plan of the step reads this buffer.'''
+        if not self.entities:
+            return None
+        w = self._wmaps.get((H, W))
+        if w is None:
+            w = self._wmaps[(H, W)] = weight_maps(self.entities, H, W).to(self.uncond_embeds.device)
+        return w
+
+    def entity_maps(self, H: int, W: int) -> torch.Tensor:
+        '''`weights(H, W)` as `fused_window_step(entities=)` takes it; without entities an empty [0][H][W] marker, which still
+        selects the composite entry point and its rep-major row count.'''
+        w = self.weights(H, W)
+        return w if w is not None else torch.empty((0, H, W), dtype=torch.float32, device=self.uncond_embeds.device)
+
+    def _check_batch(self, B: int):
+        if B != self.batch_size:
+            raise ValueError(f'latents batch {B} != the guide\'s batch_size {self.batch_size}')
+
+    def gather(self, canvas: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self._check_batch(canvas.shape[0])
+        return WindowedGuide.gather(self, canvas, out)
+
+    def step(self, x: Optional[torch.Tensor], wins: Optional[torch.Tensor], eps: torch.Tensor, coef=(0.0, 1.0, 1.0, 0.0),
+             v_prediction: bool = False, eps_out: Optional[torch.Tensor] = None, mask=None, sigma: float = 0.0,
+             step_noise=None):
+        '''`WindowedGuide.step` with the entity blend ahead of the CFG combine of every covering window: one launch
+        (fd_window_composite_step_f32), combine-only without the canvas `x`.'''
+        B, C, H, W = (x if x is not None else eps_out).shape
+        self._check_batch(B)
+        noise, draw = step_noise if step_noise is not None and sigma else (None, 0)
+        ops.window_composite_step(x, wins, eps, self.weights(H, W), B, C, self.grid(H, W).args, self.blend_code,
+                                  self.classifier_free_guidance, self.guidance, coef, v_prediction, mask, float(sigma), noise,
+                                  int(draw), do_step=x is not None, eps_out=eps_out)

@@ -8,8 +8,13 @@
 //                                 blend of masked img2img, in the same launch
 //   fd_window_multistep_step_f32  DPM-Solver++ (2M) and its SDE form on the canvas: the data prediction -> m0_out, the
 //                                 multistep update, + sn z, the blend, the next window batch
-// All three are fronts of ONE kernel, k_window_step<V, UPDATE, NOISE>, the sibling of k_latent_step (step.hip) with the
-// same three axes; the noise is the stream of philox.h at the CANVAS element, so it does not depend on the window grid.
+//   fd_window_composite_step_f32 / fd_window_composite_multistep_step_f32   region composition over windows: the guided
+//                                 prediction of every covering window is the entity blend of fd_composite_step_f32 --
+//                                 v = bg ; v = lerp(v, e_k, wmap[k]) where wmap[k] != 0, k ascending ; CFG -- and only then the
+//                                 average over the windows.  Entities live on the CANVAS: wmap is fp32 [n][H][W], read at
+//                                 the canvas cell, so a cell's weight does not depend on the window grid
+// All are fronts of ONE kernel, k_window_step<V, UPDATE, NOISE, COMP>, the sibling of k_latent_step (step.hip) with the
+// same axes; the noise is the stream of philox.h at the CANVAS element, so it does not depend on the window grid.
 // The grid travels as plain ints (H, W, h, w, stride_y, stride_x, ny, nx): along an axis of extent S with windows of
 // extent s and stride d there are n = ceil((S - s) / d) + 1 windows at offsets o_i = min(i d, S - s) -- the last one
 // snapped to the edge.  Window (iy, ix) is w = iy nx + ix; sample b, window w is row b Wn + w of the UNet batch.
@@ -22,6 +27,8 @@
 #include "window_grid.h"
 
 enum { FD_BLEND_UNIFORM = 0, FD_BLEND_TENT = 1 };
+// entities of a windowed composition: a cell's weights stay in registers across its covering windows and channel groups
+#define FD_WINDOW_MAX_ENTITIES 16
 
 // One thread owns one element of the window batch: the stores are contiguous, the loads contiguous along a window row.
 __global__ __launch_bounds__(256) void k_window_gather(const float* __restrict__ canvas, float* __restrict__ windows,
@@ -54,6 +61,9 @@ struct FdWindowStepArgs {
     float gscale, co[5], k1, k2;
     float sn;                                   // noise coefficient (NOISE kernels)
     FdNoiseAddr nz_addr;                        // per = C H W: the noise is addressed by the CANVAS element
+    const float* wmap;                          // COMP kernels: entity weights [n_ent][H][W] over the canvas
+    int n_ent;
+    size_t blk;                                 // elements per context block of eps: B Wn h w ld
 };
 
 // One thread owns one canvas cell (b, y, x) and all C channels; consecutive threads run along x, so every NCHW plane is
@@ -61,7 +71,11 @@ struct FdWindowStepArgs {
 // UPDATE, NOISE: the axes of k_latent_step (step.hip), in its order -- e -> eps_out ; the update ; + sn z ; d0 -> m0_out ; the
 // blend (mask) ; -> x and the cell of every covering window.  A thread's channels are H W apart, so the noise is looked up
 // per element: the value is a function of the canvas element's address alone, never of the window grid.
-template <int V, int UPDATE, bool NOISE>
+// COMP (n_ent > 0): eps holds cfg + 1 + n_ent blocks ([uncond] [background] [entity 0] ...), and the guided prediction of a
+// covering window is the background row with every entity lerped onto it by the weight of the CANVAS cell, in entity order,
+// w == 0 skipped exactly as k_composite_step skips it, then the CFG combine.  The n_ent weights of the cell are loaded once,
+// ahead of the channel groups and the windows.
+template <int V, int UPDATE, bool NOISE, bool COMP = false>
 __global__ __launch_bounds__(256) void k_window_step(const FdWindowStepArgs a) {
     const FdWindowGrid& g = a.g;
     const float* __restrict__ eps = a.eps;
@@ -69,12 +83,18 @@ __global__ __launch_bounds__(256) void k_window_step(const FdWindowStepArgs a) {
     const int Wn = g.ny * g.nx, hw = g.h * g.w;
     const size_t HW = (size_t)g.H * g.W;
     const size_t total = (size_t)a.B * HW;
-    const size_t half = (size_t)a.B * Wn * hw * ld;      // the conditional rows follow the unconditional ones
+    const size_t half = a.blk;                           // the conditional rows follow the unconditional ones
     for (size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (size_t)gridDim.x * blockDim.x) {
         const int px = e % g.W;
         const int py = (e / g.W) % g.H;
         const int b = e / HW;
         const float m = UPDATE != FD_STEP_NONE && a.mask ? a.mask[(size_t)py * g.W + px] : 1.f;
+        float wk[COMP ? FD_WINDOW_MAX_ENTITIES : 1];
+        if constexpr (COMP) {
+#pragma unroll
+            for (int k = 0; k < FD_WINDOW_MAX_ENTITIES; ++k)
+                wk[k] = k < a.n_ent ? a.wmap[(size_t)k * HW + (size_t)py * g.W + px] : 0.f;
+        }
         for (int c0 = 0; c0 < C; c0 += V) {
             float acc[V], last[V], u[V], t[V];
 #pragma unroll
@@ -88,7 +108,22 @@ __global__ __launch_bounds__(256) void k_window_step(const FdWindowStepArgs a) {
                     const int lx = px - fd_window_offset(ix, g.sx, g.W, g.w);
                     if (lx < 0 || lx >= g.w) continue;
                     const size_t row = (((size_t)b * Wn + iy * g.nx + ix) * hw + (size_t)ly * g.w + lx) * ld + c0;
-                    if (a.cfg) {
+                    if constexpr (COMP) {
+                        const float* bg = eps + (a.cfg ? half : 0) + row;
+                        fd_ldv<V>(bg, last);
+#pragma unroll
+                        for (int k = 0; k < FD_WINDOW_MAX_ENTITIES; ++k) {
+                            if (wk[k] == 0.f) continue;      // outside the box / masked out / k >= n_ent: exactly the background
+                            fd_ldv<V>(bg + (size_t)(k + 1) * half, t);
+#pragma unroll
+                            for (int j = 0; j < V; ++j) last[j] = fd_lerp(last[j], t[j], wk[k]);
+                        }
+                        if (a.cfg) {
+                            fd_ldv<V>(eps + row, u);
+#pragma unroll
+                            for (int j = 0; j < V; ++j) last[j] = fd_cfg_mix(u[j], last[j], a.gscale);
+                        }
+                    } else if (a.cfg) {
                         fd_ldv<V>(eps + row, u);
                         fd_ldv<V>(eps + half + row, t);
 #pragma unroll
@@ -165,8 +200,8 @@ extern "C" int fd_window_gather_f32(const float* canvas, float* windows, int B, 
     return FD_OK;
 }
 
-// ---- the host path of the three step fronts: each names the fields it sets; fd_window_step_run checks, selects, launches -------
-// the checks of the three fronts: required pointers, the combine-only form, grid, sizes, blend, the known-region blend and
+// ---- the host path of the step fronts: each names the fields it sets; fd_window_step_run checks, selects, launches -------------
+// the checks of the fronts: required pointers, the combine-only form, grid, sizes, blend, the known-region blend and
 // every alias a launch could trip over (windows_out is written while every other buffer of the call is still being read)
 static int fd_window_front_args(const char* who, int update, const FdWindowStepArgs& a) {
     FD_CHECK_ARG(a.eps, FD_EINVAL, "%s: eps_nhwc is null", who);
@@ -181,14 +216,21 @@ static int fd_window_front_args(const char* who, int update, const FdWindowStepA
     FD_TRY(fd_blend_args(who, a.x, a.z0, a.nz, a.mask, "canvas"));
     FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x, FD_EINVAL, "%s: eps_out aliases the canvas", who);
     FD_CHECK_ARG(!a.m0_out || (a.m0_out != a.x && a.m0_out != a.m1), FD_EINVAL, "%s: m0_out aliases the canvas or m1", who);
-    const void* others[] = {a.x, a.eps, a.eps_out, a.m0_out, a.m1, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr, a.mask};
+    const void* others[] = {a.x, a.eps, a.eps_out, a.m0_out, a.m1, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr, a.mask,
+                            a.n_ent > 0 ? a.wmap : nullptr};
     for (const void* o : others)
         FD_CHECK_ARG(!a.wout || a.wout != o, FD_EINVAL, "%s: windows_out aliases another buffer of the call", who);
+    // the composite fronts: the weight maps are read while the canvas-shaped outputs are written
+    FD_TRY(fd_entity_args(who, a.wmap, a.n_ent));
+    FD_CHECK_ARG(a.n_ent <= FD_WINDOW_MAX_ENTITIES, FD_EINVAL, "%s: sizes: n_entities %d, at most %d over windows", who, a.n_ent,
+                 FD_WINDOW_MAX_ENTITIES);
+    FD_CHECK_ARG(a.n_ent == 0 || (a.wmap != a.x && a.wmap != a.eps_out && a.wmap != a.m0_out), FD_EINVAL,
+                 "%s: weights alias an output of the call", who);
     return FD_OK;
 }
 
 // The checks; the noise address (sn != 0: per = C H W, the launch's first sample at sample_offset, stream 0); V = 4 when the eps
-// rows can be read as float4 along the channels, else V = 1; grid; launch.  sn == 0 launches the kernels without the noise
+// rows can be read as float4 along the channels, else V = 1; COMP when the call has entities; grid; launch.  sn == 0 launches the kernels without the noise
 // stage; the noise stage needs an update (`noise` below), so the table's holes are never read.
 static int fd_window_step_run(const char* who, int update, FdWindowStepArgs& a, uint64_t seed, int64_t sample_offset, int draw,
                               void* stream) {
@@ -200,12 +242,18 @@ static int fd_window_step_run(const char* who, int update, FdWindowStepArgs& a, 
         FD_TRY(fd_noise_addr(who, seed, sample_offset, (int)per, draw, 0, per * a.B, &a.nz_addr));
     }
     const int vec = a.C % 4 == 0 && a.ld % 4 == 0 && (uintptr_t)a.eps % 16 == 0;
-    static void (*const kernels[2][2][3])(const FdWindowStepArgs) = {
-        {{k_window_step<1, FD_STEP_NONE, false>, k_window_step<1, FD_STEP_DDIM, false>, k_window_step<1, FD_STEP_MULTISTEP, false>},
-         {k_window_step<4, FD_STEP_NONE, false>, k_window_step<4, FD_STEP_DDIM, false>, k_window_step<4, FD_STEP_MULTISTEP, false>}},
-        {{nullptr, k_window_step<1, FD_STEP_DDIM, true>, k_window_step<1, FD_STEP_MULTISTEP, true>},
-         {nullptr, k_window_step<4, FD_STEP_DDIM, true>, k_window_step<4, FD_STEP_MULTISTEP, true>}}};
-    hipLaunchKernelGGL(kernels[noise][vec][update], dim3(fd_grid1d((size_t)a.B * a.g.H * a.g.W, 2048)), dim3(256), 0,
+    a.blk = (size_t)a.B * a.g.ny * a.g.nx * a.g.h * a.g.w * a.ld;
+    const int comp = a.n_ent > 0;            // no entity: the kernels, and so the bits, of the plain fronts
+#define FD_WINDOW_KERNELS(COMP)                                                                                                 \
+    {{{k_window_step<1, FD_STEP_NONE, false, COMP>, k_window_step<1, FD_STEP_DDIM, false, COMP>,                                \
+       k_window_step<1, FD_STEP_MULTISTEP, false, COMP>},                                                                       \
+      {k_window_step<4, FD_STEP_NONE, false, COMP>, k_window_step<4, FD_STEP_DDIM, false, COMP>,                                \
+       k_window_step<4, FD_STEP_MULTISTEP, false, COMP>}},                                                                      \
+     {{nullptr, k_window_step<1, FD_STEP_DDIM, true, COMP>, k_window_step<1, FD_STEP_MULTISTEP, true, COMP>},                   \
+      {nullptr, k_window_step<4, FD_STEP_DDIM, true, COMP>, k_window_step<4, FD_STEP_MULTISTEP, true, COMP>}}}
+    static void (*const kernels[2][2][2][3])(const FdWindowStepArgs) = {FD_WINDOW_KERNELS(false), FD_WINDOW_KERNELS(true)};
+#undef FD_WINDOW_KERNELS
+    hipLaunchKernelGGL(kernels[comp][noise][vec][update], dim3(fd_grid1d((size_t)a.B * a.g.H * a.g.W, 2048)), dim3(256), 0,
                        (hipStream_t)stream, a);
     FD_CHECK_LAUNCH("k_window_step");
     return FD_OK;
@@ -255,4 +303,43 @@ extern "C" int fd_window_multistep_step_f32(float* x, float* windows_out, const 
                           .g = {H, W, h, w, stride_y, stride_x, ny, nx}, .gscale = guidance, .co = {p, q, a, w0, w1}, .k1 = k1,
                           .k2 = k2, .sn = sn};
     return fd_window_step_run("fd_window_multistep_step_f32", FD_STEP_MULTISTEP, s, seed, sample_offset, draw, stream);
+}
+
+// ---- region composition over windows: the fronts above plus `weights, n_entities` ----------------------------------------------
+extern "C" int fd_window_composite_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out,
+                                            const float* weights, int n_entities, const float* z0, const float* noise,
+                                            const float* mask, int B, int C, int ld, int H, int W, int h, int w, int stride_y,
+                                            int stride_x, int ny, int nx, int blend, int cfg, float guidance, float c1, float c2,
+                                            float c3, float c4, int v_prediction, float k1, float k2, float sigma, uint64_t seed,
+                                            int64_t sample_offset, int draw, int do_step, void* stream) {
+    FD_PLAN(fd_window_composite_step_f32(x, windows_out, eps_nhwc, eps_out, weights, n_entities, z0, noise, mask, B, C, ld, H, W,
+                                         h, w, stride_y, stride_x, ny, nx, blend, cfg, guidance, c1, c2, c3, c4, v_prediction, k1,
+                                         k2, sigma, seed, sample_offset, draw, do_step, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FD_CHECK_ARG(do_step || (!mask && sigma == 0.f), FD_EINVAL,
+                 "fd_window_composite_step_f32: the combine-only form takes neither a mask nor a sigma");
+    FdWindowStepArgs a = {.x = x, .wout = windows_out, .eps = eps_nhwc, .eps_out = eps_out, .z0 = z0, .nz = noise, .mask = mask,
+                          .B = B, .C = C, .ld = ld, .tent = blend, .cfg = cfg ? 1 : 0, .vpred = v_prediction,
+                          .g = {H, W, h, w, stride_y, stride_x, ny, nx}, .gscale = guidance, .co = {c1, c2, c3, c4}, .k1 = k1,
+                          .k2 = k2, .sn = sigma, .wmap = weights, .n_ent = n_entities};
+    return fd_window_step_run("fd_window_composite_step_f32", do_step ? FD_STEP_DDIM : FD_STEP_NONE, a, seed, sample_offset, draw,
+                              stream);
+}
+
+extern "C" int fd_window_composite_multistep_step_f32(float* x, float* windows_out, const float* eps_nhwc, const float* weights,
+                                                      int n_entities, float* m0_out, const float* m1, const float* z0,
+                                                      const float* noise, const float* mask, int B, int C, int ld, int H, int W,
+                                                      int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg,
+                                                      float guidance, float p, float q, float a, float w0, float w1, float k1,
+                                                      float k2, float sn, uint64_t seed, int64_t sample_offset, int draw,
+                                                      void* stream) {
+    FD_PLAN(fd_window_composite_multistep_step_f32(x, windows_out, eps_nhwc, weights, n_entities, m0_out, m1, z0, noise, mask, B,
+                                                   C, ld, H, W, h, w, stride_y, stride_x, ny, nx, blend, cfg, guidance, p, q, a, w0,
+                                                   w1, k1, k2, sn, seed, sample_offset, draw, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FdWindowStepArgs s = {.x = x, .wout = windows_out, .eps = eps_nhwc, .m0_out = m0_out, .m1 = m1, .z0 = z0, .nz = noise,
+                          .mask = mask, .B = B, .C = C, .ld = ld, .tent = blend, .cfg = cfg ? 1 : 0,
+                          .g = {H, W, h, w, stride_y, stride_x, ny, nx}, .gscale = guidance, .co = {p, q, a, w0, w1}, .k1 = k1,
+                          .k2 = k2, .sn = sn, .wmap = weights, .n_ent = n_entities};
+    return fd_window_step_run("fd_window_composite_multistep_step_f32", FD_STEP_MULTISTEP, s, seed, sample_offset, draw, stream);
 }

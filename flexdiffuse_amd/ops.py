@@ -1382,6 +1382,54 @@ def window_multistep_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], 
                  _floats(coef, 5), (float(sn), *_noise_address(noise, sn), int(draw)))
 
 
+def _window_entities(eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], B: int, C: int, grid, cfg: bool):
+    '''`_guided_rows` over a window batch: eps_nhwc holds at least (cfg + 1 + n) B Wn h w rows, n the entities of `weights`,
+    fp32 [n][H][W] over the CANVAS (None or n == 0: none).  Returns the (weights, n) a windowed composite front hands the
+    library.'''
+    H, W, h, w, _, _, ny, nx = grid
+    n = 0 if weights is None else int(weights.shape[0])
+    if n:
+        _check_f32(n * H * W, weights)
+    _check_eps_rows(eps_nhwc, ((1 if cfg else 0) + 1 + n) * B * ny * nx * h * w, C)
+    return (_p(weights) if n else None), n
+
+
+def window_composite_step(x: Optional[torch.Tensor], windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor,
+                          weights: Optional[torch.Tensor], B: int, C: int, grid, blend: int, cfg: bool, guidance: float,
+                          coef=(0.0, 1.0, 1.0, 0.0), v_prediction: bool = False, mask=None, sigma: float = 0.0, noise=None,
+                          draw: int = 0, do_step: bool = True, eps_out: Optional[torch.Tensor] = None):
+    '''Region composition over windows (fd_window_composite_step_f32): `window_step` / `window_ddim_step` whose guided
+    prediction per covering window is `composite_step`'s entity blend.  eps_nhwc [(cfg + 1 + n) * B Wn * h w][ld] fp32 in
+    rep-major order over the window batch, weights [n][H][W] fp32 over the canvas (None: no entity, the bits of
+    `window_ddim_step`).  do_step False: the combine-only form (eps_out required; no windows_out, mask or sigma).'''
+    H, W, h, w, _, _, ny, nx = grid
+    wp, n = _window_entities(eps_nhwc, weights, B, C, grid, cfg)
+    z0, nz, mk, k1, k2 = _blend(mask, H * W, B * C * H * W)
+    _check_f32(B * C * H * W, x, eps_out)
+    _check_f32(B * ny * nx * C * h * w, windows_out)
+    hip.call('fd_window_composite_step_f32', _p(x), _p(windows_out), eps_nhwc.data_ptr(), _p(eps_out), wp, n, _p(z0), _p(nz),
+             _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg), float(guidance), *_floats(coef, 4),
+             int(v_prediction), k1, k2, float(sigma), *_noise_address(noise, sigma), int(draw), int(do_step), hip.stream())
+
+
+def window_composite_multistep_step(x: torch.Tensor, windows_out: Optional[torch.Tensor], eps_nhwc: torch.Tensor,
+                                    weights: Optional[torch.Tensor], m0_out: torch.Tensor, m1: Optional[torch.Tensor], B: int,
+                                    C: int, grid, blend: int, cfg: bool, guidance: float, coef, mask=None, sn: float = 0.0,
+                                    noise=None, draw: int = 0):
+    '''Region composition over windows under DPM-Solver++ (fd_window_composite_multistep_step_f32): `window_multistep_step`,
+    argument for argument, on the entity blend + CFG of `window_composite_step`'s rows with the canvas maps `weights`
+    [n][H][W] -- one launch.'''
+    assert m0_out is not None
+    H, W, h, w, _, _, ny, nx = grid
+    wp, n = _window_entities(eps_nhwc, weights, B, C, grid, cfg)
+    z0, nz, mk, k1, k2 = _blend(mask, H * W, B * C * H * W)
+    _check_f32(B * C * H * W, x, m0_out, m1)
+    _check_f32(B * ny * nx * C * h * w, windows_out)
+    hip.call('fd_window_composite_multistep_step_f32', _p(x), _p(windows_out), eps_nhwc.data_ptr(), wp, n, m0_out.data_ptr(),
+             _p(m1), _p(z0), _p(nz), _p(mk), B, C, eps_nhwc.stride(0), *(int(v) for v in grid), int(blend), int(cfg),
+             float(guidance), *_floats(coef, 5), k1, k2, float(sn), *_noise_address(noise, sn), int(draw), hip.stream())
+
+
 def axpby(x: torch.Tensor, y: Optional[torch.Tensor], a: float, b: float,
           exp_half_x: bool = False) -> torch.Tensor:
     assert x.dtype == torch.float32 and (y is None or (y.dtype == torch.float32 and y.numel() == x.numel())), \

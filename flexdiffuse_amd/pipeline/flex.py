@@ -29,7 +29,9 @@ request's state (`_begin`), and a loop that calls ONE step method per iteration 
     Without it `eta > 0` is the generator route, as the reference forwards `eta` to its scheduler (pipeline/flex.py:247-251);
   - guidance rescale (`guide.guidance_rescale`; Lin et al. 2023 sec. 3.4) inside the step's launch or the combine-only launch;
   - windowed sampling (`WindowedGuide`; MultiDiffusion, windows.py): the window batch is the loop's persistent buffer and ONE
-    launch per step combines, averages, steps the canvas and writes the next window batch.
+    launch per step combines, averages, steps the canvas and writes the next window batch;
+  - region composition over windows (`WindowedCompositeGuide`): that loop with E context blocks over the window batch and the
+    entity blend, per covering window, inside the same one launch.
 The step launches of the simple guide are one kernel (csrc/step.hip) over one statement of the step arithmetic
 (csrc/latent_step.h), which the composite's launches call too: the routes are bit-equal wherever they compute the same thing.
 
@@ -103,6 +105,7 @@ class _Request():
         # the CFG switch of a simple or composite guide, the UNet's batch replication, DDIM's prediction type
         self.cfg, self.rep, self.vpred = None, 1, False
         self.ent = {}                              # {'entities': the composite's weight maps [n][HW]} when they ride in the step
+                                                   # (a windowed composite's: [n][H][W] over the canvas)
         self.grid = self.wins = None               # window loops: the grid and the persistent window batch
         self.lin_input = None                      # K-LMS on the linear loop: the persistent, sigma-scaled model input
 
@@ -428,6 +431,9 @@ class FlexPipeline():
                 s.wins = torch.empty(wshape, dtype=torch.float32, device=latents.device)
                 self._lat_bufs = {wshape: s.wins}
             guide.gather(latents, s.wins)
+            if hasattr(guide, 'entity_maps'):
+                # a WindowedCompositeGuide: its canvas weight maps [n][H][W] ride in the multistep launch (its own `step` carries them)
+                s.ent = {'entities': guide.entity_maps(H, W)}
         return s, latents
 
     def _eps(self, s: _Request, x: torch.Tensor, t: int, latents: torch.Tensor):
@@ -510,7 +516,7 @@ class FlexPipeline():
         if r.multistep:
             self.scheduler.fused_window_step(latents, s.wins, eps, int(t), s.B, s.C, s.grid.args, guide.blend_code,
                                              guide.classifier_free_guidance, guide.guidance, s.mask(i),
-                                             (s.step_noise, s.t_start + i) if r.sde else None)
+                                             (s.step_noise, s.t_start + i) if r.sde else None, **s.ent)
         else:
             coef = self.scheduler.step_coefficients(int(t), s.eta if r.noisy else 0.0)
             guide.step(latents, s.wins, eps, coef[:4], s.vpred, mask=s.mask(i), sigma=float(coef[4]) if r.noisy else 0.0,

@@ -104,7 +104,8 @@ class WindowedGuide(SimpleGuide):
     The step noise is addressed by the canvas element, so it does not depend on the window grid.  Every other scheduler
     (PNDM, K-LMS, DDIM eta > 0 on generator noise) takes the planned route: one gather, the UNet replay, the combine-only
     form, `scheduler.step` -- the bits of the `noise_pred` loop.  `guidance_rescale` is not supported (its standard
-    deviations would have to span the canvas), nor is a CompositeGuide over windows.'''
+    deviations would have to span the canvas).  Region composition over windows is the subclass
+    `composition.guide.WindowedCompositeGuide`: the same routes, the entity blend inside the same one launch.'''
 
     def __init__(self, encoder, unet, guidance: float, steps: int, clip_embeds: torch.Tensor, *, window=(512, 512),
                  stride=(256, 256), blend: str = 'uniform', guidance_rescale: float = 0.0):

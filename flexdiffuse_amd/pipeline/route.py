@@ -5,7 +5,7 @@ tensor.  This is the route table (DESIGN.md sec. 7 keeps the history of the feat
 The guide kind (by whose `noise_pred` the guide's class has; everything needs a UNet with `forward_nhwc`):
   simple      SimpleGuide's own (ScheduledGuide included)
   composite   CompositeGuide's own, with `fuse_composite` on or a batched / masked guide (`on_device`)
-  window      WindowedGuide's own
+  window      WindowedGuide's own (WindowedCompositeGuide included: it inherits it, and carries its entities in its `step`)
   other       anything else: the reference protocol
 `fuse` below: a simple guide, or a composite one with `fuse_composite` on (`fuse_entities`: the entity blend rides in the
 step's launch).  `on`: graph or plan in use and `debug` off.  `noise`: `pipe.step_noise` given, or an SDE scheduler (which
@@ -28,9 +28,13 @@ gets one from the generator's seed).  The first row that applies is the route:
                                                                            `scheduler.step`, the blend-only launch of a mask image
   window             DPM-Solver++ and SDE; DDIM, eta = 0   window          one launch over the window batch: fd_window_step_f32 |
                      | eta > 0, noise                                      fd_window_ddim_step_f32 (mask image or eta > 0) |
-                                                                           fd_window_multistep_step_f32
+                                                                           fd_window_multistep_step_f32; a
+                                                                           WindowedCompositeGuide: fd_window_composite_step_f32 |
+                                                                           fd_window_composite_multistep_step_f32
   window             any other; on                         window_planned  fd_window_gather_f32, the replay, the combine-only
-                                                                           fd_window_step_f32, `scheduler.step`, the blend-only launch
+                                                                           fd_window_step_f32 (a WindowedCompositeGuide: of
+                                                                           fd_window_composite_step_f32), `scheduler.step`, the
+                                                                           blend-only launch
   any                any                                   generic         `guide.noise_pred`, `scheduler.step`, the blend-only launch
 
 `ddim`, `multistep` and `linear` (PLMS) step in the persistent buffer the graph / plan reads when `on` (`persistent`); every

@@ -594,12 +594,19 @@ class DPMSolverMultistepScheduler(_Configured):
         return {}
 
     def fused_window_step(self, canvas: torch.Tensor, wins: Optional[torch.Tensor], eps_nhwc: torch.Tensor, timestep, B: int,
-                          C: int, grid_args, blend: int, cfg: bool, guidance: float, mask=None, step_noise=None):
+                          C: int, grid_args, blend: int, cfg: bool, guidance: float, mask=None, step_noise=None, entities=None):
         '''`fused_step` on the canvas of a windowed request (fd_window_multistep_step_f32): `eps_nhwc` is the UNet output over
         the window batch; one launch takes CFG per window, the average where windows overlap, x0 into the history, the
         update, the blend of `mask` = (z0, noise, mask [H W], k1, k2) and writes the next window batch into `wins`.  The
         history is canvas-shaped.  `step_noise`: the SDE subclass's (PhiloxNoise, draw).  A method of its own:
-        `fused_step`'s signature is pinned.'''
+        `fused_step`'s signature is pinned.  `entities`: the canvas weight maps fp32 [n][H][W] of a WindowedCompositeGuide
+        (n == 0: an empty marker) -- eps_nhwc then holds its (cfg + 1 + n) B Wn h w rep-major rows and the entity blend precedes
+        the CFG combine of every covering window in the same one launch (fd_window_composite_multistep_step_f32).'''
+        if entities is not None:
+            self._fused(canvas, timestep, lambda i, m0, m1, co: ops.window_composite_multistep_step(
+                canvas, wins, eps_nhwc, entities, m0, m1, B, C, grid_args, blend, cfg, guidance, co[:5], mask,
+                **self._rescale_noise(i, co, step_noise)))
+            return
         self._fused(canvas, timestep, lambda i, m0, m1, co: ops.window_multistep_step(
             canvas, wins, eps_nhwc, m0, m1, B, C, grid_args, blend, cfg, guidance, co[:5], mask,
             **self._rescale_noise(i, co, step_noise)))

@@ -26,7 +26,7 @@ import torch
 from . import build
 from .encode.clip import CLIPEncoder
 from .guidance import Guide
-from .composition import CompositeGuide, EntitySchema, Schema
+from .composition import CompositeGuide, EntitySchema, Schema, WindowedCompositeGuide
 from .noise import PhiloxNoise
 from .pipeline.guide import GuideBase, ScheduledGuide, SimpleGuide, WindowedGuide
 from .scheduler import DPMSolverMultistepSDEScheduler
@@ -262,7 +262,22 @@ class Runner():
         given.apply_defaults()
         return self._compose(dict(given.arguments), style_linear)
 
-    def _compose(self, given: Dict[str, Any], style_linear=None):
+    def compose_wide(self, bg_prompt: str = '', entities_df: Sequence[Sequence[Any]] = (), *, size: Tuple[int, int] = (512, 1536),
+                     window=512, stride=256, blend: str = 'uniform', **compose_args):
+        '''`compose` on a canvas larger or wider than the model's size (beyond the reference; `WindowedCompositeGuide`): a
+        background prompt plus entity prompts in rectangles or soft masks given in CANVAS pixels, over `gen_wide`'s
+        windows -- `size` is the image's (height, width), covered by overlapping `window`s at `stride` (image pixels; an
+        int means both axes) whose predictions, each with the entities blended in, are averaged ('uniform') or tent-weighted
+        ('tent') where they overlap.  Every other argument is `compose`'s, by keyword (`compose` itself keeps the
+        reference's signature): `batch_size`, `masks`, `init_image` / `mask_image` of canvas size, `seed`, `steps`;
+        `init_size` is `size`.  `Runner.guidance_rescale` is refused, as by `gen_wide`.'''
+        given = inspect.signature(Runner.compose).bind(self, bg_prompt, entities_df, **compose_args)
+        given.apply_defaults()
+        given = dict(given.arguments)
+        given['init_size'] = tuple(size)
+        return self._compose(given, wide=(window, stride, blend))
+
+    def _compose(self, given: Dict[str, Any], style_linear=None, wide=None):
         (bg_prompt, entities_df, start_style, end_style, style_blend, init_image, batches, strength, steps, guidance_scale,
          init_size, seed, debug, batch_size, masks, mask_image) = (given[k] for k in (
              'bg_prompt', 'entities_df', 'start_style', 'end_style', 'style_blend', 'init_image', 'batches', 'strength',
@@ -280,7 +295,15 @@ class Runner():
         extra = {'batch_size': batch_size} if batch_size != 1 else {}
         if style_linear is not None:
             extra['style_linear'] = style_linear
-        guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps, **extra)
+        if wide is not None:
+            window, stride, blend = wide
+            if self.guidance_rescale:
+                raise ValueError('compose_wide does not support Runner.guidance_rescale: its standard deviations would have to '
+                                 'span the canvas')
+            guide = WindowedCompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps,
+                                           window=window, stride=stride, blend=blend, **extra)
+        else:
+            guide = CompositeGuide(self.encoder, self.pipe.unet, guidance_scale, self.last_schema, steps, **extra)
         # (only when given: a subclass's `_run` with the reference's six arguments keeps working)
         return self._run(batches, guide, init_image, init_size, strength, debug,
                          **({'mask_image': mask_image} if mask_image is not None else {}))

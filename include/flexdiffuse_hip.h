@@ -707,6 +707,48 @@ int fd_window_multistep_step_f32(float* x, float* windows_out, const float* eps_
                                  int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg, float guidance,
                                  float p, float q, float a, float w0, float w1, float k1, float k2, float sn, uint64_t seed,
                                  int64_t sample_offset, int draw, void* stream);
+/* Region composition over windows, one launch per step (additive; FD_ABI_VERSION stays 12): the fronts above with the entity
+ * blend of fd_composite_step_f32 as the source of the guided prediction of every covering window -- the same kernel
+ * (k_window_step, csrc/window.hip), the arguments of the sibling plus `weights, n_entities`.  Entities live on the CANVAS:
+ * weights is fp32 [n_entities][H][W] over the canvas latent, shared by the B samples, read at the canvas cell (y, x); a cell's
+ * weight does not depend on the window grid.  The UNet batch is the window batch (B Wn latent rows, sample b, window w at row
+ * b Wn + w) under E = cfg + 1 + n_entities context blocks in rep-major order ([uncond] [background] [entity 0] ...): in
+ * eps_nhwc block r, sample b, window w, local cell (ly, lx) is row ((r B + b) Wn + w) h w + ly w + lx, row stride ld >= C.
+ * With first = cfg ? 1 : 0, per canvas cell (b, y, x) and channel, every operation a separately rounded fp32 one:
+ *   for every window covering the cell, in ascending (iy, ix) order, R_r its row in block r:
+ *     v = eps[R_first]
+ *     for k = 0 .. n_entities - 1, ascending:  wk = weights[(k H + y) W + x] ;  wk != 0:  v = v + wk (eps[R_(first + 1 + k)] - v)
+ *       (the wk == 0 skip is an exact branch and there is none for wk == 1: the lerp is the contract, as in
+ *       fd_composite_step_f32)
+ *     g_w = cfg ? u + guidance (v - u), u = eps[R_0] : v
+ *     acc, wsum as fd_window_step_f32 (uniform | tent)
+ *   e = g_w where exactly one window covers the cell, else acc / count | acc / wsum, as fd_window_step_f32
+ *   then every stage of the sibling in its order: eps_out, the update, + sigma z at the canvas element, m0_out, the
+ *   known-region blend, x, and the cell of every covering window in windows_out.
+ * Blend and CFG are linear and the weights do not depend on the window, so this equals averaging each block first and blending
+ * afterwards up to rounding; per window first keeps one accumulator set instead of E.  The rows of an (entity, window) pair
+ * that do not intersect are read nowhere (weight 0).  n_entities == 0 (weights ignored): the sibling's kernel and bits.  A
+ * one-window grid gives the bits of fd_composite_ddim_step_f32 / fd_composite_multistep_step_f32; an entity that is 0 on the
+ * whole canvas those of the call without its block.  float4 loads along the channels under the sibling's rule (C % 4 == 0,
+ * ld % 4 == 0, eps_nhwc 16-byte aligned); the weights of a cell are scalar loads, once per cell.
+ * FD_EINVAL before any launch: the sibling's cases; n_entities < 0 or above 16; weights NULL with n_entities > 0; weights
+ * aliasing windows_out, x, eps_out or m0_out.
+ * fd_window_composite_step_f32 replaces fd_window_step_f32 and fd_window_ddim_step_f32 for a composition: do_step == 0 is the
+ * combine-only form (eps_out required, windows_out, mask NULL and sigma 0; x may be NULL); do_step == 1 the DDIM step with the
+ * optional sigma z term and the optional known-region blend. */
+int fd_window_composite_step_f32(float* x, float* windows_out, const float* eps_nhwc, float* eps_out, const float* weights,
+                                 int n_entities, const float* z0, const float* noise, const float* mask, int B, int C, int ld,
+                                 int H, int W, int h, int w, int stride_y, int stride_x, int ny, int nx, int blend, int cfg,
+                                 float guidance, float c1, float c2, float c3, float c4, int v_prediction, float k1, float k2,
+                                 float sigma, uint64_t seed, int64_t sample_offset, int draw, int do_step, void* stream);
+/* fd_window_composite_multistep_step_f32 replaces fd_window_multistep_step_f32 for a composition: DPM-Solver++ (2M), orders 1
+ * (m1 == NULL) and 2, sn == 0 the ODE form. */
+int fd_window_composite_multistep_step_f32(float* x, float* windows_out, const float* eps_nhwc, const float* weights,
+                                           int n_entities, float* m0_out, const float* m1, const float* z0, const float* noise,
+                                           const float* mask, int B, int C, int ld, int H, int W, int h, int w, int stride_y,
+                                           int stride_x, int ny, int nx, int blend, int cfg, float guidance, float p, float q,
+                                           float a, float w0, float w1, float k1, float k2, float sn, uint64_t seed,
+                                           int64_t sample_offset, int draw, void* stream);
 /* Tiled VAE decode / encode (additive; FD_ABI_VERSION stays 12): the VAE runs on a batch of overlapping tiles of the model's
  * own size -- the grid of fd_window_gather_f32, same rule, same batch order -- and this one launch puts the tile outputs
  * together.  tiles: NHWC fp32, the row of (sample b, tile t = iy nx + ix, ly, lx) is ((b ny nx + t) h + ly) w + lx, row
