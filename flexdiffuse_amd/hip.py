@@ -122,6 +122,7 @@ _SIGNATURES = {
     'fd_window_composite_multistep_step_f32': (c_int, [P] * 4 + [c_int] + [P] * 5 + [c_int] * 13 + [c_float] * 9
                                                + [c_uint64, c_int64, c_int, P]),
     'fd_tile_blend_f32': (c_int, [P, P] + [c_int] * 13 + [c_float, c_float, c_int, P]),
+    'fd_latent_upscale_noise_f32': (c_int, [P] * 4 + [c_int] * 14 + [c_float, c_float, c_uint64, c_int64, c_int, c_int, P]),
     'fd_cast_f32_to_f16':(c_int, [P, P, c_int64, P]),
     'fd_cast_f16_to_f32': (c_int, [P, P, c_int64, P]),
 }

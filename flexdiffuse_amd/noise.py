@@ -5,6 +5,11 @@ by the 64-bit seed on the counter (element >> 2, sample, draw, stream), then Box
 kernels generate it in registers (stream 0, draw = the step's index in the scheduler's timestep list); nothing here is
 ever drawn on the host.  `sample_offset` is the global index of a call's first sample, so a batch split over ranks
 (`dist.sample_offset`) or over sequential calls (`utils.Runner`) sees the noise of the one large batch.
+
+Streams: 0 (`STREAM_STEP`) the step noise of the step kernels, 1 (`STREAM_FILL`) the stand-alone fill, 2 (`STREAM_INIT`) the
+start noise of a request that begins from clean latents (`FlexPipeline.__call__(init_latents=)`, the second pass of hires
+sampling): draw 0, generated inside fd_latent_upscale_noise_f32 at the canvas element, so the values are those of
+`PhiloxNoise.normal((B, C, H, W), 0, stream=STREAM_INIT)` and never collide with a step's draw.
 '''
 from __future__ import annotations
 
@@ -12,7 +17,7 @@ from typing import Sequence
 
 import torch
 
-STREAM_STEP, STREAM_FILL = 0, 1
+STREAM_STEP, STREAM_FILL, STREAM_INIT = 0, 1, 2
 
 
 class PhiloxNoise():

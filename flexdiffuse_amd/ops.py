@@ -1316,6 +1316,38 @@ def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, g
     hip.call('fd_window_gather_f32', canvas.data_ptr(), windows.data_ptr(), B, C, *(int(v) for v in grid), hip.stream())
 
 
+UPSCALE_MODES = {'nearest': 0, 'bilinear': 1, 'bicubic': 2}
+
+
+def latent_upscale_noise(src: torch.Tensor, x: torch.Tensor, mode='bicubic', k1: float = 1.0, k2: float = 0.0, noise=None,
+                         draw: int = 0, noise_stream: int = 2, windows_out: Optional[torch.Tensor] = None, grid=None) -> torch.Tensor:
+    '''The bridge of hires sampling (fd_latent_upscale_noise_f32), one launch: src (1 | B, C, hs, ws) resampled onto the canvas
+    x (B, C, H, W), H >= hs and W >= ws, both NCHW fp32 -- `mode` 'nearest', or the antialiased 'bilinear' / 'bicubic' of
+    torch's interpolate(antialias=True) -- and x = k1 r + k2 z in `axpby`'s arithmetic.  `noise`: a
+    tensor shaped like x, or a `PhiloxNoise` whose stream (`draw`, `noise_stream`, addressed by the canvas element) is generated
+    in the kernel; k2 == 0: no noise stage.  Given `windows_out` (B Wn, C, h, w) and `grid` (`windows.WindowGrid.args` over
+    (H, W)), the same values land in the cell of every covering window: the canvas and its `window_gather` at once.'''
+    B, C, H, W = x.shape
+    n, Cs, hs, ws = src.shape
+    assert Cs == C and n in (1, B), (tuple(src.shape), tuple(x.shape))
+    _check_f32(n * C * hs * ws, src)
+    _check_f32(B * C * H * W, x)
+    hip.require_device(src, x, windows_out)
+    g = (0,) * 6
+    if windows_out is not None:
+        assert grid is not None and (int(grid[0]), int(grid[1])) == (H, W), (grid, H, W)
+        _check_f32(B * grid[6] * grid[7] * C * grid[2] * grid[3], windows_out)
+        g = tuple(int(v) for v in grid[2:])
+    tensor = isinstance(noise, torch.Tensor)
+    if tensor:
+        _check_f32(B * C * H * W, noise)
+        hip.require_device(noise)
+    seed, offset = (0, 0) if tensor else _noise_address(noise, k2)
+    hip.call('fd_latent_upscale_noise_f32', src.data_ptr(), x.data_ptr(), _p(windows_out), noise.data_ptr() if tensor else None,
+             B, n, C, hs, ws, H, W, *g, UPSCALE_MODES[mode], float(k1), float(k2), seed, offset, int(draw), int(noise_stream), hip.stream())
+    return x
+
+
 def tile_blend(tiles: torch.Tensor, B: int, C: int, grid, feather, a: float = 1.0, b: float = 0.0, clamp01: bool = False,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:
     '''Tile batch -> canvas (fd_tile_blend_f32): tiles [B Tn * h w][ld] NHWC fp32 rows in fd_window_gather_f32's batch order

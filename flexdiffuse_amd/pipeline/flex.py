@@ -31,7 +31,10 @@ request's state (`_begin`), and a loop that calls ONE step method per iteration 
   - windowed sampling (`WindowedGuide`; MultiDiffusion, windows.py): the window batch is the loop's persistent buffer and ONE
     launch per step combines, averages, steps the canvas and writes the next window batch;
   - region composition over windows (`WindowedCompositeGuide`): that loop with E context blocks over the window batch and the
-    entity blend, per covering window, inside the same one launch.
+    entity blend, per covering window, inside the same one launch;
+  - two-pass hires sampling (`hires`, `from_latents`): a request may start from clean latents, which ONE launch
+    (fd_latent_upscale_noise_f32) resamples onto the canvas, noises to the start level and -- on the `window` route -- scatters
+    into the window batch; `output_type='latent'` hands the first pass's latents over without a VAE pass.
 The step launches of the simple guide are one kernel (csrc/step.hip) over one statement of the step arithmetic
 (csrc/latent_step.h), which the composite's launches call too: the routes are bit-equal wherever they compute the same thing.
 
@@ -51,7 +54,7 @@ import torch
 
 from .. import hip, ops
 from ..encode.clip import preprocess
-from ..noise import PhiloxNoise
+from ..noise import STREAM_INIT, PhiloxNoise
 from ..scheduler import LMSDiscreteScheduler
 from .guide import GuideBase, check_guidance_rescale
 from .inpaint import image_size, known_coefficients, latent_mask, start_level
@@ -365,18 +368,12 @@ class FlexPipeline():
         init_latents = self.vae.encode(init_image).latent_dist.sample(generator=generator)
         init_latents = ops.axpby(init_latents, None, VAE_SCALE, 0.0)
         init_latents = torch.cat([init_latents] * batch_size)
-        offset = self.scheduler.config.get('steps_offset', 0)
-        init_timestep = min(int(guide.steps * strength) + offset, guide.steps)
-        if isinstance(self.scheduler, LMSDiscreteScheduler):
-            t_noise = guide.steps - init_timestep     # pipeline/flex.py:200-204: an index
-        else:
-            t_noise = int(self.scheduler.timesteps[-init_timestep])
+        t_noise, t_start = self._start_of(guide.steps, strength)
         # one level per sample, as a long tensor (pipeline/flex.py:201-209); built on the host
         t_noise = torch.tensor([t_noise] * batch_size, dtype=torch.long)
         noise = self._randn(init_latents.shape, generator) if noise is None else noise.to(self.device, torch.float32)
         if tuple(noise.shape) != tuple(init_latents.shape):
             raise ValueError(f'noise {tuple(noise.shape)} does not match the latents {tuple(init_latents.shape)}')
-        t_start = max(guide.steps - init_timestep + offset, 0)
         known = None
         if mask_image is not None:
             # z0 and n stay alive for the loop; add_noise returns a new tensor, so neither aliases the latents
@@ -390,12 +387,67 @@ class FlexPipeline():
                 self.scheduler, self.scheduler.timesteps, t_start, start_level(self.scheduler, int(t_noise[0]))))
         return self.scheduler.add_noise(init_latents, noise, t_noise), t_start, known
 
+    def _start_of(self, steps: int, strength: float) -> Tuple[int, int]:
+        '''(t_noise, t_start) of an img2img request (pipeline/flex.py:195-216): the level its first latents are noised to -- a
+        timestep, under K-LMS a sigma index (:200-204) -- and the index of its first timestep.'''
+        offset = self.scheduler.config.get('steps_offset', 0)
+        init_timestep = min(int(steps * strength) + offset, steps)
+        if isinstance(self.scheduler, LMSDiscreteScheduler):
+            t_noise = steps - init_timestep
+        else:
+            t_noise = int(self.scheduler.timesteps[-init_timestep])
+        return t_noise, max(steps - init_timestep + offset, 0)
+
+    def _noise_level(self, t_noise: int) -> Tuple[float, float]:
+        '''The (k1, k2) of `scheduler.add_noise(z0, n, t_noise)` = k1 z0 + k2 n, the floats it hands its one launch.'''
+        if isinstance(self.scheduler, LMSDiscreteScheduler):
+            return 1.0, float(self.scheduler.sigmas[t_noise])
+        a = self.scheduler.alphas_cumprod[t_noise]
+        return float(np.sqrt(a)), float(np.sqrt(np.float32(1.0) - a))
+
+    def _init_from_latents(self, guide, init_latents, init_size, strength, generator, noise, upscale, route: Route):
+        '''The first latents of a request that starts from clean latents (`from_latents`; the second pass of hires sampling):
+        they are resampled onto the canvas of `init_size` and noised to the start level of an img2img request of `strength` by
+        ONE launch (fd_latent_upscale_noise_f32) -- no VAE, no host copy, and with `pipe.step_noise` no noise tensor.  The
+        noise: the `noise=` tensor, else the stream of `pipe.step_noise` (stream STREAM_INIT, draw 0, generated in the kernel
+        at the canvas element), else one host draw of the generator, as img2img draws it.  -> (canvas, t_start, bridge):
+        on the `window` route the launch also writes the first window batch, so it is handed to `_begin`, which owns that
+        buffer, as `bridge`; on every other route it has been issued here and `bridge` is None.'''
+        B, C = guide.batch_size, self.unet.in_channels
+        H, W = init_size[0] // 8, init_size[1] // 8
+        if init_latents.dim() != 4 or init_latents.shape[0] not in (1, B) or init_latents.shape[1] != C:
+            raise ValueError(f'init_latents {tuple(init_latents.shape)} are not (1 | {B}, {C}, h, w)')
+        hs, ws = init_latents.shape[-2:]
+        if H < hs or W < ws:
+            raise ValueError(f'the canvas {(H, W)} of init_size {tuple(init_size)} is smaller than init_latents {(hs, ws)}: only '
+                             'upscaling is supported')
+        src = init_latents.to(self.device, torch.float32).contiguous()
+        t_noise, t_start = self._start_of(guide.steps, strength)
+        k1, k2 = self._noise_level(t_noise)
+        if noise is not None:
+            noise = noise.to(self.device, torch.float32).contiguous()
+            if tuple(noise.shape) != (B, C, H, W):
+                raise ValueError(f'noise {tuple(noise.shape)} does not match the latents {(B, C, H, W)}')
+        elif self.step_noise is not None:
+            noise = self.step_noise
+        else:
+            noise = self._randn((B, C, H, W), generator)
+        canvas = torch.empty((B, C, H, W), dtype=torch.float32, device=self.device)
+
+        def bridge(wins=None, grid=None):
+            ops.latent_upscale_noise(src, canvas, upscale, k1, k2, noise, 0, STREAM_INIT, wins, grid)
+        if route.loop == 'window':
+            return canvas, t_start, bridge
+        bridge()
+        return canvas, t_start, None
+
     def _lin_scale(self, j: int) -> float:
         return 1.0 / ((float(self.scheduler.sigmas[j]) ** 2 + 1) ** 0.5)     # pipeline/flex.py:270-274
 
-    def _begin(self, route: Route, guide, latents, t_start, known, eta, step_noise, debug):
+    def _begin(self, route: Route, guide, latents, t_start, known, eta, step_noise, debug, bridge=None):
         '''The request's state and the tensor its loop steps: the persistent buffers a route reads through the graph / plan, the
-        time-embedding table, the composite's weight maps, the window batch.  -> (_Request, latents).'''
+        time-embedding table, the composite's weight maps, the window batch.  `bridge` (`_init_from_latents`, the `window`
+        route): the one launch that fills `latents` and the window batch, instead of the gather.  -> (_Request, latents).'''
         B, C, H, W = latents.shape
         s = _Request(route, guide, (B, C, H, W), t_start, known, eta, step_noise, debug)
         if route.persistent:
@@ -430,7 +482,10 @@ class FlexPipeline():
             if s.wins is None:
                 s.wins = torch.empty(wshape, dtype=torch.float32, device=latents.device)
                 self._lat_bufs = {wshape: s.wins}
-            guide.gather(latents, s.wins)
+            if bridge is not None:
+                bridge(s.wins, s.grid.args)
+            else:
+                guide.gather(latents, s.wins)
             if hasattr(guide, 'entity_maps'):
                 # a WindowedCompositeGuide: its canvas weight maps [n][H][W] ride in the multistep launch (its own `step` carries them)
                 s.ent = {'entities': guide.entity_maps(H, W)}
@@ -583,7 +638,36 @@ class FlexPipeline():
         every scheduler step the kept region of the latents is put back on the clean init latents re-noised with
         the call's own noise to the step's level (`inpaint.known_coefficients`), on the last step on the clean init
         latents themselves.  The image is the VAE decode of the blended latents: pasting the original pixels back
-        over the kept region is out of scope, as are per-sample masks and feathering helpers.'''
+        over the kept region is out of scope, as are per-sample masks and feathering helpers.
+
+        `output_type='latent'` (beyond the reference): the final latents (B, 4, h, w) come back as the images, a tensor of
+        the caller's own, and the VAE does not run.'''
+        return self._sample(guide, init_image, init_size, strength, eta, generator, output_type, return_dict, debug, latents,
+                            noise, mask_image)
+
+    @torch.no_grad()
+    def from_latents(self, guide: GuideBase, init_latents: torch.Tensor, *, init_size: Tuple[int, int] = (512, 512),
+                     strength: float = 0.6, upscale: str = 'bicubic', eta: float = 0.0,
+                     generator: Optional[torch.Generator] = None, output_type: str = 'pil', return_dict: bool = True,
+                     debug: bool = False, noise: Optional[torch.Tensor] = None):
+        '''An img2img request that starts from clean latents instead of an image (beyond the reference; the second pass of
+        hires sampling, `hires`): `init_latents`, already scaled, (1 | B, 4, hs, ws) -- one latent may be shared by the B
+        samples, each with its own noise -- are resampled onto the canvas of `init_size` (`upscale`: 'nearest', or the
+        antialiased 'bilinear' / 'bicubic' of the reference's composition/guide.py:27-29 `_scale`; the canvas may not be
+        smaller) and noised to the level `strength` gives an init image (`steps_offset` and K-LMS's index form included),
+        all in ONE launch (`_init_from_latents`): no VAE pass, no host copy.  `noise`: canvas-shaped add_noise rows instead
+        of the pipeline's own.  Every other argument is `__call__`'s, by keyword (`__call__` itself keeps the reference's
+        signature); there is no init image and so no mask image.'''
+        if upscale not in ops.UPSCALE_MODES:
+            raise ValueError(f'upscale should be one of {sorted(ops.UPSCALE_MODES)} but is {upscale!r}')
+        if not isinstance(init_latents, torch.Tensor):
+            raise ValueError(f'init_latents should be a tensor (1 | B, 4, h, w) but are {type(init_latents).__name__}')
+        return self._sample(guide, None, init_size, strength, eta, generator, output_type, return_dict, debug, None, noise, None,
+                            init_latents, upscale)
+
+    def _sample(self, guide, init_image, init_size, strength, eta, generator, output_type, return_dict, debug, latents, noise,
+                mask_image, init_latents=None, upscale='bicubic'):
+        '''The request behind `__call__` and `from_latents`.'''
         if strength < 0 or strength > 1:
             raise ValueError(
                 f'The value of strength should in [0.0, 1.0] but is {strength}')
@@ -598,13 +682,20 @@ class FlexPipeline():
         route = select_route(guide, self.scheduler, self.unet, eta=eta, step_noise=self.step_noise, rescale=rescale, debug=debug,
                              use_graph=self.use_graph, use_plan=self.use_plan, fuse_composite=self.fuse_composite,
                              fuse_linear_multistep=self.fuse_linear_multistep)
-        latents, t_start, known = self._init_latents(guide, init_image, init_size, strength, generator, latents, noise, mask_image)
+        bridge = None
+        if init_latents is not None:
+            latents, t_start, bridge = self._init_from_latents(guide, init_latents, init_size, strength, generator, noise, upscale,
+                                                               route)
+            known = None
+        else:
+            latents, t_start, known = self._init_latents(guide, init_image, init_size, strength, generator, latents, noise,
+                                                         mask_image)
         all_latents = [latents] if debug else None
         # the step noise of the request: the pipeline's attribute; an SDE scheduler without one gets the generator's seed
         step_noise = self.step_noise
         if route.sde and step_noise is None:
             step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
-        s, latents = self._begin(route, guide, latents.contiguous(), t_start, known, eta, step_noise, debug)
+        s, latents = self._begin(route, guide, latents.contiguous(), t_start, known, eta, step_noise, debug, bridge)
         step = {'ddim': self._step_ddim, 'multistep': self._step_multistep, 'linear': self._step_linear,
                 'window': self._step_window}.get(route.loop, self._step_generic)
         # a guide with a context schedule (ScheduledGuide, CompositeGuide(style_linear=)): told the GLOBAL step index at the top of
@@ -626,7 +717,9 @@ class FlexPipeline():
             persistent = any(latents is b for b in self._lat_bufs.values())
             self.last_latents = latents.clone() if persistent else latents
 
-            if all_latents:
+            if output_type == 'latent':
+                batch_images = self.last_latents
+            elif all_latents:
                 batches = [self._latents_to_image(l, output_type == 'pil') for l in all_latents]
                 if isinstance(batches[0], list):
                     batch_images = [im for ib in batches for im in ib]
@@ -639,3 +732,19 @@ class FlexPipeline():
             return (batch_images, False)
         return StableDiffusionPipelineOutput(images=batch_images,
                                              nsfw_content_detected=[False for _ in batch_images])
+
+    def hires(self, guide: GuideBase, hires_guide: GuideBase, *, init_size: Tuple[int, int], hires_size: Tuple[int, int],
+              hires_strength: float = 0.5, upscale: str = 'bicubic', eta: float = 0.0,
+              generator: Optional[torch.Generator] = None, output_type: str = 'pil', return_dict: bool = True):
+        '''Two-pass ("hires fix") sampling, beyond the reference: `guide` samples at `init_size`, the model's own size, which
+        fixes the layout; its latents are upscaled to `hires_size`, noised back to the level of `hires_strength` and finished
+        by `hires_guide` as an img2img request -- typically a `WindowedGuide` over the same embeddings, so every UNet launch
+        stays at the model's size.  The two explicit calls, `self(guide, output_type='latent')` and
+        `self.from_latents(hires_guide, ...)`, nothing else: between them is one launch (`_init_from_latents`), no VAE pass
+        and no host copy.  The guides may be any pair with one `batch_size` (a CompositeGuide / WindowedCompositeGuide pair
+        included, with the second one's entities given on its own canvas).'''
+        if guide.batch_size != hires_guide.batch_size:
+            raise ValueError(f'the guides of the two passes differ in batch_size: {guide.batch_size} and {hires_guide.batch_size}')
+        base = self(guide, init_size=init_size, eta=eta, generator=generator, output_type='latent', return_dict=False)[0]
+        return self.from_latents(hires_guide, base, init_size=hires_size, strength=hires_strength, upscale=upscale, eta=eta,
+                                 generator=generator, output_type=output_type, return_dict=return_dict)

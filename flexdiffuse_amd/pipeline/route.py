@@ -37,6 +37,14 @@ gets one from the generator's seed).  The first row that applies is the route:
                                                                            blend-only launch
   any                any                                   generic         `guide.noise_pred`, `scheduler.step`, the blend-only launch
 
+Ahead of the loop, a request that starts from clean latents (`FlexPipeline.from_latents`, the second pass of `hires`) makes ONE
+launch, fd_latent_upscale_noise_f32 (upscale + add_noise; the noise in-kernel with `pipe.step_noise`), in place of add_noise:
+
+  loop               the pre-loop launch writes            then
+  window             the canvas AND the window batch       nothing: no fd_window_gather_f32, no fd_axpby_f32
+  any other          the canvas (windows_out = NULL)       the route's own setup, unchanged (the copy into the persistent buffer,
+                                                           K-LMS's scaled input, `window_planned`'s gather)
+
 `ddim`, `multistep` and `linear` (PLMS) step in the persistent buffer the graph / plan reads when `on` (`persistent`); every
 loop but `generic` reads the request's time-embedding table (`temb_table`).  Guidance rescale applies to a simple guide only
 (any other applies or ignores its own attribute in its `noise_pred`) and is refused for a window guide.  On `planned`,

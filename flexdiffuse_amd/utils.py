@@ -132,18 +132,26 @@ class Runner():
         self.generator.manual_seed(seed)
         return seed
 
-    def _run(self, batches: int, guide: GuideBase, init_image, init_size: Tuple[int, int],
-             strength: float, debug: bool, mask_image=None):
-        '''`batches` sequential pipeline calls on one generator stream -- the reference's only
-        data-parallel axis (utils.py:90) -- and the grid of everything they produced.'''
+    def _apply_vae_tiling(self):
+        '''`vae_tiling` onto the pipeline's VAE, at the top of every run.'''
         # a pipeline around a foreign VAE (`_decode_generic`) has no tiling to switch off
         if self.vae_tiling:
             self.pipe.enable_vae_tiling(*(() if self.vae_tiling is True else self.vae_tiling))
         elif getattr(getattr(self.pipe, 'vae', None), 'tiling', None) is not None:
             self.pipe.disable_vae_tiling()
+
+    def _stochastic(self) -> bool:
+        '''Whether a run keys the pipeline's counter-based noise by the generator's seed: `step_noise`, or an SDE scheduler.'''
+        return bool(self.step_noise or isinstance(self.pipe.scheduler, DPMSolverMultistepSDEScheduler))
+
+    def _run(self, batches: int, guide: GuideBase, init_image, init_size: Tuple[int, int],
+             strength: float, debug: bool, mask_image=None):
+        '''`batches` sequential pipeline calls on one generator stream -- the reference's only
+        data-parallel axis (utils.py:90) -- and the grid of everything they produced.'''
+        self._apply_vae_tiling()
         images: List[Any] = []
         extra = {'mask_image': mask_image} if mask_image is not None else {}
-        stochastic = self.step_noise or isinstance(self.pipe.scheduler, DPMSolverMultistepSDEScheduler)
+        stochastic = self._stochastic()
         for k in range(batches):
             if stochastic:
                 self.pipe.step_noise = PhiloxNoise(self.generator.initial_seed(), sample_offset=k * guide.batch_size)
@@ -199,6 +207,39 @@ class Runner():
         given = dict(given.arguments)
         given['init_size'] = tuple(size)
         return self._gen(given, wide=(window, stride, blend))
+
+    def gen_hires(self, prompt='', *, size: Tuple[int, int] = (1024, 1024), base_size: Tuple[int, int] = (512, 512),
+                  hires_strength: float = 0.5, hires_steps: Optional[int] = None, upscale: str = 'bicubic', window=512,
+                  stride=256, blend: str = 'tent', **gen_args):
+        '''Two-pass ("hires fix") sampling (beyond the reference; `FlexPipeline.hires`): `gen` at `base_size`, the model's own
+        size, then its latents upscaled (`upscale`) to the canvas of `size`, noised back to the level of `hires_strength`
+        and finished by `gen_wide`'s windows (`window`, `stride`, `blend`) over the same embeddings in `hires_steps`
+        (default: `steps`) -- one launch between the passes instead of a VAE decode, a host resize and a VAE encode.  Every
+        other argument is `gen`'s, by keyword (`init_size`, `strength` and `debug` are not read: the passes have their own
+        sizes and level, and return no intermediate images); the prompt is embedded once.  `init_image` / `mask_image` and `Runner.guidance_rescale` are refused; `vae_tiling` and
+        `step_noise` are honoured.'''
+        given = inspect.signature(Runner.gen).bind(self, prompt, **gen_args)
+        given.apply_defaults()
+        given = dict(given.arguments)
+        if given['init_image'] is not None or given['mask_image'] is not None:
+            raise ValueError('gen_hires starts from noise at base_size: it takes neither an init_image nor a mask_image')
+        if self.guidance_rescale:
+            raise ValueError('gen_hires does not support Runner.guidance_rescale: its second pass is windowed, and the standard '
+                             'deviations would have to span the canvas')
+        self._set_seed(given['seed'])
+        unet, scale, steps = self.pipe.unet, given['guidance_scale'], given['steps']
+        embeds = self.guide.embeds(prompt=given['prompt'], guide=given['guide'], **{k: given[k] for k in _EMBEDS_KEYS})
+        first = SimpleGuide(self.encoder, unet, scale, steps, embeds)
+        second = WindowedGuide(self.encoder, unet, scale, hires_steps or steps, embeds, window=window, stride=stride, blend=blend)
+        self._apply_vae_tiling()
+        images: List[Any] = []
+        for k in range(given['samples']):
+            if self._stochastic():
+                self.pipe.step_noise = PhiloxNoise(self.generator.initial_seed(), sample_offset=k * first.batch_size)
+            result = self.pipe.hires(first, second, init_size=tuple(base_size), hires_size=tuple(size),
+                                     hires_strength=hires_strength, upscale=upscale, eta=self.eta, generator=self.generator)
+            images += list(result['sample'])
+        return images, image_grid(images)
 
     def _gen(self, given: Dict[str, Any], travel=None, wide=None):
         self._set_seed(given['seed'])

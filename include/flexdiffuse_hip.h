@@ -765,6 +765,42 @@ int fd_window_composite_multistep_step_f32(float* x, float* windows_out, const f
  * FD_EINVAL: the grid's errors; NULL tiles or out; ld < C; a feather below 1; out overlapping tiles. */
 int fd_tile_blend_f32(const float* tiles, float* out, int B, int C, int ld, int H, int W, int h, int w, int stride_y,
                       int stride_x, int ny, int nx, int feather_y, int feather_x, float a, float b, int clamp01, void* stream);
+/* Hires two-pass sampling, the bridge between the passes (additive; FD_ABI_VERSION stays 12; csrc/resample.hip): ONE launch
+ * resamples low-resolution latents onto a canvas, noises them to the start level of the second pass and, on a windowed canvas,
+ * writes the first window batch.  src: (src_samples, C, hs, ws) NCHW fp32, src_samples 1 (one latent shared by the B samples,
+ * each with its own noise) or B.  x: (B, C, H, W) NCHW fp32, H >= hs and W >= ws (FD_ESHAPE otherwise: downscaling would need
+ * the antialias filter widened).  Per canvas cell (b, y, x) and channel, o = ((b C + c) H + y) W + x, every operation a
+ * separately rounded fp32 one:
+ *   r = sum over the row taps jy (ascending) of wy[jy] (sum over the column taps jx (ascending) of wx[jx] src[b mod src_samples][c][jy][jx]),
+ *       each sum starting at its first product (no zero seed)
+ *   z = noise[o] (noise != NULL) | the counter-based normal (fd_philox_normal_f32) of canvas element o: per = C H W,
+ *       sample = sample_offset + b, draw, noise_stream -- the fill of a (B, C, H, W) tensor at that element | 0 when k2 == 0
+ *       (no noise stage: noise, seed, sample_offset, draw and noise_stream are ignored)
+ *   x[o] = k1 r + k2 z (two products, one sum): the bits of fd_axpby_f32(r, z, k1, k2), which is scheduler.add_noise
+ *   windows_out (optional) <- the same value in the cell of every covering window of the grid (h, w, stride_y, stride_x, ny, nx):
+ *       fd_window_gather_f32's rule, checks and layout; each window cell has one source, so there are no atomics.  With
+ *       windows_out == NULL the six grid ints are ignored.
+ * The taps of output index i along an axis n_in -> n_out (align_corners = False conventions):
+ *   n_out == n_in: the one tap j = i with weight 1 (an exact branch: the identity in every mode)
+ *   mode 0 (nearest): the one tap j = ((2 i + 1) n_in) / (2 n_out) in integer arithmetic, weight 1
+ *   mode 1 (bilinear, S = 1, f the triangle 1 - |t|) and mode 2 (bicubic, S = 2, f the Keys cubic with a = -0.5:
+ *   ((1.5 t - 2.5) t) t + 1 for |t| < 1, (((t - 5) t + 8) t - 4) (-0.5) for |t| < 2, else 0): the filters of torch's
+ *   interpolate(..., antialias=True), which is the reference's composition/guide.py:27-29 --
+ *     c = (n_in / n_out) (i + 0.5) ;  j in [max(0, floor(c - S + 0.5)), min(n_in, floor(c + S + 0.5))) ;  f_j = f(j - c + 0.5)
+ *     w_j = f_j / (f_lo + ... + f_hi-1)   (taps that fall off the axis are dropped, not clamped; at most 2 | 4 taps)
+ *   c is the ratio of the integers m = n_in (2 i + 1) and d = 2 n_out: the two floors are exact integer divisions and the
+ *   filter argument is the ONE rounded quotient (d j + n_out - m) / d of two exact integers, so a weight is accurate to an ulp
+ *   of its argument whatever the extent of the axis (torch's own fp32 c loses ulp(c)).  The filter's Horner steps, the sum
+ *   of the f_j (from f_lo on) and the quotients are separately rounded.
+ *   NOT torch's non-antialiased bicubic (a = -0.75, clamped indices).
+ * A cell's value depends on neither the grid nor the launch shape.  One thread owns one canvas cell and its C channels.
+ * FD_EINVAL: NULL src or x; non-positive sizes; src_samples not in {1, B}; an unknown mode; the grid's errors when windows_out is
+ * given; src, x, windows_out, noise overlapping; H or W past 2^24, cells past 2^31; with in-kernel noise (k2 != 0, noise == NULL) C H W past 2^31,
+ * a negative sample_offset, draw or noise_stream, or sample_offset + B past 2^32. */
+int fd_latent_upscale_noise_f32(const float* src, float* x, float* windows_out, const float* noise, int B, int src_samples,
+                                int C, int hs, int ws, int H, int W, int h, int w, int stride_y, int stride_x, int ny, int nx,
+                                int mode, float k1, float k2, uint64_t seed, int64_t sample_offset, int draw, int noise_stream,
+                                void* stream);
 /* Contiguous casts: fp32 -> fp16 rounds to nearest even (overflow to inf from 65520 on), fp16 -> fp32 is exact. */
 int fd_cast_f32_to_f16(const float* x, void* y, int64_t n, void* stream);
 int fd_cast_f16_to_f32(const void* x, float* y, int64_t n, void* stream);
