@@ -17,7 +17,7 @@ from .pipeline.guide import GuideBase, PromptGuide, ScheduledGuide, SimpleGuide,
 from .composition.guide import CompositeGuide, WindowedCompositeGuide  # noqa: E402,F401
 from .noise import PhiloxNoise  # noqa: E402,F401
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler,  # noqa: E402,F401
-                        LMSDiscreteScheduler, PNDMScheduler)
+                        LMSDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
 from .tokenizer import SyntheticTokenizer  # noqa: E402,F401
 from .build import build_models, load_state_dicts, load_tokenizer, synthetic_state_dicts  # noqa: E402,F401
 from .utils import Runner, image_grid  # noqa: E402,F401

@@ -8,7 +8,8 @@ import torch
 
 from . import weights as W
 from .clip import CLIPModel
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler, PNDMScheduler
+from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler, PNDMScheduler,
+                        UniPCMultistepScheduler)
 from .tokenizer import SyntheticTokenizer
 from .unet import UNet2DConditionModel
 from .vae import AutoencoderKL
@@ -176,7 +177,7 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
     '''The scheduler the checkpoint itself ships (`sd_dir`/scheduler/scheduler_config.json), which is what the
     reference passes into its pipeline (utils.py:70: `sd.scheduler` -- PNDM/PLMS for CompVis/stable-diffusion-v1-4, so a
     50-step request is 51 UNet evaluations).  `_class_name` -> PNDMScheduler / LMSDiscreteScheduler / DDIMScheduler /
-    DPMSolverMultistepScheduler with the betas, `skip_prk_steps`, `steps_offset`, `set_alpha_to_one`, `clip_sample`,
+    DPMSolverMultistepScheduler / UniPCMultistepScheduler with the betas, `skip_prk_steps`, `steps_offset`, `set_alpha_to_one`, `clip_sample`,
     `solver_order`, `lower_order_final`, `rescale_betas_zero_snr` and (DDIM) `timestep_spacing` of the file.  None when the checkpoint has
     no scheduler folder; NotImplementedError for a class this package does not provide (never a silent substitute).'''
     import json
@@ -229,8 +230,20 @@ def load_scheduler(sd_dir: str, prediction_type: str = 'epsilon'):
         return DPMSolverMultistepScheduler(**common, solver_order=cfg.get('solver_order', 2), prediction_type=ptype,
                                            lower_order_final=cfg.get('lower_order_final', True),
                                            rescale_betas_zero_snr=zero_snr)
+    if name == 'UniPCMultistepScheduler':
+        # the data-prediction form with its corrector on every step, on the linspace grid, is what is provided
+        for key, default, ok in (('predict_x0', True, (True,)), ('solver_type', 'bh2', ('bh1', 'bh2')), ('solver_order', 2, (1, 2, 3)),
+                                 ('thresholding', False, (False,)), ('disable_corrector', [], ([], None)),
+                                 ('use_karras_sigmas', False, (False,)), ('timestep_spacing', 'linspace', ('linspace',)),
+                                 ('rescale_betas_zero_snr', False, (False,))):
+            if cfg.get(key, default) not in ok:
+                raise NotImplementedError(f'{path}: UniPCMultistepScheduler with {key}={cfg[key]!r} is not provided '
+                                          f'(only {", ".join(repr(v) for v in ok)}); pass scheduler= to choose one explicitly')
+        return UniPCMultistepScheduler(**common, solver_order=cfg.get('solver_order', 2), solver_type=cfg.get('solver_type', 'bh2'),
+                                       prediction_type=ptype, lower_order_final=cfg.get('lower_order_final', True))
     raise NotImplementedError(f'{path}: scheduler class {name!r} is not provided (PNDMScheduler, LMSDiscreteScheduler, '
-                              'DDIMScheduler, DPMSolverMultistepScheduler are); pass scheduler= to choose one explicitly')
+                              'DDIMScheduler, DPMSolverMultistepScheduler, UniPCMultistepScheduler are); pass scheduler= to choose '
+                              'one explicitly')
 
 
 def from_directories(sd_dir: str, clip_dir: str, tokenizer_dir: Optional[str] = None, preset: str = 'sd15',

@@ -1,7 +1,8 @@
 // The per-step arithmetic on the fp32 latents, stated ONCE: classifier-free guidance, the DDIM (eta = 0) update and the
-// known-region blend of masked img2img, the DPM-Solver++ multistep update and the linear multistep updates of PLMS and K-LMS.
+// known-region blend of masked img2img, the DPM-Solver++ multistep update, the linear multistep updates of PLMS and K-LMS and
+// the corrector + predictor pair of UniPC.
 // k_latent_step (step.hip: fd_cfg_ddim_step_f32, fd_cfg_ddim_masked_step_f32, fd_cfg_multistep_step_f32,
-// fd_cfg_linear_multistep_step_f32), k_window_step (window.hip), k_composite_step (composite.hip) and
+// fd_cfg_linear_multistep_step_f32, fd_cfg_unipc_step_f32), k_window_step (window.hip), k_composite_step (composite.hip) and
 // k_region_blend (elementwise.hip) all call these, so
 // the product's contract -- those entry points are bit-equal to each other and to an fp32 torch restatement in the same
 // order -- holds by construction.  Every operation is a separately rounded fp32 intrinsic: the library builds with
@@ -10,7 +11,7 @@
 #include "common.h"
 
 // the update a step kernel is instantiated for (k_latent_step, k_window_step)
-enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2, FD_STEP_LINEAR = 3 };
+enum { FD_STEP_NONE = 0, FD_STEP_DDIM = 1, FD_STEP_MULTISTEP = 2, FD_STEP_LINEAR = 3, FD_STEP_UNIPC = 4 };
 
 // a + w (b - a)
 __device__ __forceinline__ float fd_lerp(float a, float b, float w) { return __fadd_rn(a, __fmul_rn(w, __fsub_rn(b, a))); }
@@ -64,6 +65,33 @@ __device__ __forceinline__ float fd_klms_update(float x, float e, const float (&
 #pragma unroll
     for (int k = 1; k <= 3; ++k)
         if (k <= n_prev) xn = __fadd_rn(__fmul_rn(1.f, xn), __fmul_rn(c[k], h[k - 1]));
+    return xn;
+}
+
+// UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"), data
+// prediction, both stages as the linear forms of UniPCMultistepScheduler.step_coefficients.  h: the x0 rows of the earlier
+// steps, newest first; xl: the corrected sample the previous step's predictor started from.
+//   m = p x + q e                                     (pq; the data prediction at the sample the model saw: the history's next row)
+//   xc = cx xl + cn m, then xc += c_k h_k, k = 1..c_ord   (uc = (cx, cn, c_1, c_2, c_3); UniC at the previous predictor's order;
+//                                                          c_ord == 0: no corrector, xc = x)
+//   x' = ax xc + w0 m, then x' += w_k h_k, k = 1..p_ord - 1   (up = (ax, w0, w_1, w_2); UniP)
+// Each sum in that order: the sample's term, then m, then the rows newest first.  At p_ord <= 2 without a corrector this is
+// fd_multistep_update's arithmetic on (p, q, ax, w0, w_1).
+__device__ __forceinline__ float fd_unipc_update(float x, float xl, float e, const float (&h)[3], int c_ord, int p_ord,
+                                                 const float (&pq)[5], const float (&uc)[5], const float (&up)[4], float& m,
+                                                 float& xc) {
+    m = __fadd_rn(__fmul_rn(pq[0], x), __fmul_rn(pq[1], e));
+    xc = x;
+    if (c_ord >= 1) {
+        xc = __fadd_rn(__fmul_rn(uc[0], xl), __fmul_rn(uc[1], m));
+#pragma unroll
+        for (int k = 1; k <= 3; ++k)
+            if (k <= c_ord) xc = __fadd_rn(xc, __fmul_rn(uc[k + 1], h[k - 1]));
+    }
+    float xn = __fadd_rn(__fmul_rn(up[0], xc), __fmul_rn(up[1], m));
+#pragma unroll
+    for (int k = 1; k <= 2; ++k)
+        if (k < p_ord) xn = __fadd_rn(xn, __fmul_rn(up[k + 1], h[k - 1]));
     return xn;
 }
 

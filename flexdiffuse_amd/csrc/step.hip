@@ -8,6 +8,12 @@
 //                                (guided eps | the derivative) -> h_out, the linear multistep update over up to three earlier
 //                                rows (latent_step.h: fd_plms_update, fd_klms_update), the blend, and for K-LMS the next
 //                                step's scaled model input -> x_scaled_out
+//   fd_cfg_unipc_step_f32        UniPC (Zhao et al. 2023; UniPCMultistepScheduler): CFG combine, the data prediction m = p x + q e
+//                                -> m_out, the corrector UniC of the sample the previous step predicted from (x_last and up to
+//                                three earlier rows) -> x_keep_out, the predictor UniP from the corrected sample (m and up to two
+//                                of those rows), the blend (latent_step.h: fd_unipc_update); fd_cfg_rescale_unipc_step_f32 and
+//                                fd_composite_unipc_step_f32 are its rescaled and its composite form.  The kept sample is updated
+//                                IN PLACE: x_keep_out may be x_last, because a thread reads and writes only its own elements
 //   fd_cfg_ddim_noise_step_f32, fd_cfg_multistep_noise_step_f32   the stochastic forms (DDIM eta > 0, SDE-DPM-Solver++):
 //                                the same steps plus x' += sn z, z the counter-based normal stream of philox.h generated
 //                                in the kernel; fd_philox_normal_f32 writes that stream out on its own
@@ -50,6 +56,11 @@ struct FdStepArgs {
     // cfg + 1 + n_ent blocks of B HW rows in rep-major order
     const float* wmap;
     int n_ent;
+    // FD_STEP_UNIPC only (zero elsewhere): co = (p, q); x_src: the sample the corrector starts from, x_keep: the corrected sample
+    // (may be x_src); rows m1, h2, h3 as above; uc = (cx, cn, c1, c2, c3) at order c_ord (0: no corrector), up = (ax, w0, w1, w2)
+    // at order p_ord
+    int c_ord, p_ord;
+    float uc[5], up[4];
 };
 
 // One thread owns V consecutive pixels of one (b, c) plane.  V = 4: HW % 4 == 0 and 16-byte bases, so a group never
@@ -129,6 +140,22 @@ __device__ __forceinline__ void fd_step_group(const FdStepArgs& a, size_t e, int
             }
         }
         if (a.form != 0) fd_stv<V>(a.m0_out + e, ev);
+    } else if constexpr (UPDATE == FD_STEP_UNIPC) {
+        const int rows = a.c_ord > a.p_ord - 1 ? a.c_ord : a.p_ord - 1;      // rows of unused orders are never read
+        float h[3][V], lv[V], cv[V];
+        if (rows >= 1) fd_ldv<V>(a.m1 + e, h[0]);
+        if (rows >= 2) fd_ldv<V>(a.h2 + e, h[1]);
+        if (rows >= 3) fd_ldv<V>(a.h3 + e, h[2]);
+        if (a.c_ord >= 1) fd_ldv<V>(a.x_src + e, lv);
+#pragma unroll
+        for (int j = 0; j < V; ++j) {
+            const float hj[3] = {rows >= 1 ? h[0][j] : 0.f, rows >= 2 ? h[1][j] : 0.f, rows >= 3 ? h[2][j] : 0.f};
+            float m;
+            xv[j] = fd_unipc_update(xv[j], a.c_ord >= 1 ? lv[j] : 0.f, ev[j], hj, a.c_ord, a.p_ord, a.co, a.uc, a.up, m, cv[j]);
+            ev[j] = m;
+        }
+        fd_stv<V>(a.m0_out + e, ev);
+        fd_stv<V>(a.x_keep + e, cv);                            // (x_keep may be x_src: this thread's own elements, read above)
     }
     if constexpr (NOISE) {
         float sv[V];
@@ -254,7 +281,7 @@ static int fd_step_check(const char* who, int update, FdStepArgs& a, unsigned fl
     // required pointers (the CFG combine alone, -> eps_out, touches no x)
     FD_CHECK_ARG(a.eps || (flags & FD_EPS_OPTIONAL), FD_EINVAL, "%s: eps_nhwc is null", who);
     FD_CHECK_ARG(a.x || (update == FD_STEP_NONE && !a.mask), FD_EINVAL, "%s: x is null", who);
-    FD_CHECK_ARG(a.m0_out || update != FD_STEP_MULTISTEP, FD_EINVAL, "%s: m0_out is null", who);
+    FD_CHECK_ARG(a.m0_out || (update != FD_STEP_MULTISTEP && update != FD_STEP_UNIPC), FD_EINVAL, "%s: m0_out is null", who);
     FD_CHECK_ARG(!(flags & FD_BLEND_REQUIRED) || (a.z0 && a.nz && a.mask), FD_EINVAL, "%s: z0, noise or mask is null", who);
     FD_TRY(fd_step_sizes(who, a.B, a.C, a.HW, a.ld, a.eps != nullptr));
     if (rs) {                                                        // k_latent_step_rescale counts a sample in 32 bits
@@ -272,15 +299,26 @@ static int fd_step_check(const char* who, int update, FdStepArgs& a, unsigned fl
         FD_CHECK_ARG(a.form == 0 || (a.m0_out && !a.x_src && !a.x_keep), FD_EINVAL,
                      "%s: K-LMS needs h_out (null) and takes neither x_src nor x_keep_out", who);
     }
+    if (update == FD_STEP_UNIPC) {
+        FD_CHECK_ARG(a.c_ord >= 0 && a.c_ord <= 3, FD_EINVAL, "%s: corrector order %d is outside 0..3", who, a.c_ord);
+        FD_CHECK_ARG(a.p_ord >= 1 && a.p_ord <= 3, FD_EINVAL, "%s: predictor order %d is outside 1..3", who, a.p_ord);
+        const float* const rows[3] = {a.m1, a.h2, a.h3};
+        for (int k = 0; k < a.c_ord || k < a.p_ord - 1; ++k)
+            FD_CHECK_ARG(rows[k], FD_EINVAL, "%s: history row h%d is null with orders %d, %d", who, k + 1, a.c_ord, a.p_ord);
+        FD_CHECK_ARG(a.x_keep && (a.x_src || a.c_ord == 0), FD_EINVAL, "%s: x_keep_out is null, or x_last is null with a corrector", who);
+    }
     FD_TRY(fd_entity_args(who, a.wmap, a.n_ent));
     FD_TRY(fd_blend_args(who, a.x, a.z0, a.nz, a.mask, "latents"));
     // no output on a buffer the launch still reads (x, the history rows, x_src, the known region) or on another output
     FD_CHECK_ARG(!a.eps_out || a.eps_out != a.x || (flags & FD_EPS_OUT_ON_X), FD_EINVAL, "%s: eps_out aliases the latents", who);
     const float* const reads[7] = {a.x, a.m1, a.h2, a.h3, a.x_src, a.mask ? a.z0 : nullptr, a.mask ? a.nz : nullptr};
     float* const outs[2] = {a.m0_out, a.x_keep};
+    const bool ring = update == FD_STEP_LINEAR || update == FD_STEP_UNIPC;
     for (int o = 0; o < 2; ++o)
-        for (int r = 0; outs[o] && r < (update == FD_STEP_LINEAR ? 7 : 2); ++r)      // multistep: m0_out against x and m1
+        for (int r = 0; outs[o] && r < (ring ? 7 : 2); ++r) {                        // multistep: m0_out against x and m1
+            if (update == FD_STEP_UNIPC && o == 1 && r == 4) continue;               // UniPC keeps its corrected sample in place
             FD_CHECK_ARG(outs[o] != reads[r], FD_EINVAL, "%s: m0_out / h_out / x_keep_out alias the latents or a row that is read", who);
+        }
     FD_CHECK_ARG(!a.m0_out || a.m0_out != a.x_keep, FD_EINVAL, "%s: h_out and x_keep_out alias each other", who);
     FD_CHECK_ARG(!a.x_scaled || (a.x_scaled != a.x && a.x_scaled != a.m0_out && a.x_scaled != a.x_keep), FD_EINVAL,
                  "%s: x_scaled_out aliases the latents or another output", who);
@@ -308,31 +346,37 @@ static FdStepVec fd_step_vec(int update, const FdStepArgs& a) {
 }
 
 // The kernel of (rescale, comp, noise, vec, update), or NULL where none is instantiated -- a noise stage without an update or
-// on the linear update, composition without an update, rescale on the linear update or together with composition: the caller
-// refuses those before the launch.  Rows in the order [composition | plain | rescale][noise][vec][update].
+// on the linear or the UniPC update, composition without an update, rescale on the linear update or together with composition:
+// the caller refuses those before the launch.  Rows in the order [composition | plain | rescale][noise][vec][update].
 static const void* fd_step_kernel(bool rescale, bool comp, bool noise, bool vec, int update) {
 #define FD_K(...) ((const void*)(__VA_ARGS__))
-    static const void* const kernels[3][2][2][4] = {
+    static const void* const kernels[3][2][2][5] = {
         {{{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, false, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, false, true>),
-           FD_K(k_latent_step<1, FD_STEP_LINEAR, false, true>)},
+           FD_K(k_latent_step<1, FD_STEP_LINEAR, false, true>), FD_K(k_latent_step<1, FD_STEP_UNIPC, false, true>)},
           {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, false, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, false, true>),
-           FD_K(k_latent_step<4, FD_STEP_LINEAR, false, true>)}},
-         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true, true>), nullptr},
-          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true, true>), nullptr}}},
+           FD_K(k_latent_step<4, FD_STEP_LINEAR, false, true>), FD_K(k_latent_step<4, FD_STEP_UNIPC, false, true>)}},
+         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true, true>), nullptr,
+           nullptr},
+          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true, true>), nullptr,
+           nullptr}}},
         {{{FD_K(k_latent_step<1, FD_STEP_NONE, false>), FD_K(k_latent_step<1, FD_STEP_DDIM, false>),
-           FD_K(k_latent_step<1, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<1, FD_STEP_LINEAR, false>)},
+           FD_K(k_latent_step<1, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<1, FD_STEP_LINEAR, false>),
+           FD_K(k_latent_step<1, FD_STEP_UNIPC, false>)},
           {FD_K(k_latent_step<4, FD_STEP_NONE, false>), FD_K(k_latent_step<4, FD_STEP_DDIM, false>),
-           FD_K(k_latent_step<4, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<4, FD_STEP_LINEAR, false>)}},
-         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true>), nullptr},
-          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true>), nullptr}}},
+           FD_K(k_latent_step<4, FD_STEP_MULTISTEP, false>), FD_K(k_latent_step<4, FD_STEP_LINEAR, false>),
+           FD_K(k_latent_step<4, FD_STEP_UNIPC, false>)}},
+         {{nullptr, FD_K(k_latent_step<1, FD_STEP_DDIM, true>), FD_K(k_latent_step<1, FD_STEP_MULTISTEP, true>), nullptr, nullptr},
+          {nullptr, FD_K(k_latent_step<4, FD_STEP_DDIM, true>), FD_K(k_latent_step<4, FD_STEP_MULTISTEP, true>), nullptr, nullptr}}},
         {{{FD_K(k_latent_step_rescale<1, FD_STEP_NONE, false>), FD_K(k_latent_step_rescale<1, FD_STEP_DDIM, false>),
-           FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, false>), nullptr},
+           FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, false>), nullptr, FD_K(k_latent_step_rescale<1, FD_STEP_UNIPC, false>)},
           {FD_K(k_latent_step_rescale<4, FD_STEP_NONE, false>), FD_K(k_latent_step_rescale<4, FD_STEP_DDIM, false>),
-           FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, false>), nullptr}},
-         {{nullptr, FD_K(k_latent_step_rescale<1, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, true>), nullptr},
-          {nullptr, FD_K(k_latent_step_rescale<4, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, true>), nullptr}}}};
+           FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, false>), nullptr, FD_K(k_latent_step_rescale<4, FD_STEP_UNIPC, false>)}},
+         {{nullptr, FD_K(k_latent_step_rescale<1, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<1, FD_STEP_MULTISTEP, true>), nullptr,
+           nullptr},
+          {nullptr, FD_K(k_latent_step_rescale<4, FD_STEP_DDIM, true>), FD_K(k_latent_step_rescale<4, FD_STEP_MULTISTEP, true>), nullptr,
+           nullptr}}}};
 #undef FD_K
-    if ((rescale && comp) || update < FD_STEP_NONE || update > FD_STEP_LINEAR) return nullptr;
+    if ((rescale && comp) || update < FD_STEP_NONE || update > FD_STEP_UNIPC) return nullptr;
     return kernels[rescale ? 2 : comp ? 0 : 1][noise][vec][update];
 }
 
@@ -523,6 +567,59 @@ extern "C" int fd_cfg_rescale_multistep_step_f32(float* x, const float* eps_nhwc
     const FdStepRescale rs = {rescale, scale_out};
     return fd_step_run("fd_cfg_rescale_multistep_step_f32", FD_STEP_MULTISTEP, s, stream, 0, &nz, &rs);
 }
+
+// ---- UniPC: the plain (and masked), the rescaled and the composite form ---------------------------------------------------
+// Rows of unused orders and the x_last of a step without a corrector are dropped here: never read, never counted by the vector rule.
+#define FD_UNIPC_FIELDS                                                                                                          \
+    .x = x, .eps = eps_nhwc, .eps_out = eps_out, .m0_out = m_out, .m1 = c_order >= 1 || p_order >= 2 ? h1 : nullptr, .z0 = z0, \
+    .nz = noise, .mask = mask, .B = B, .C = C, .HW = HW, .ld = ld, .cfg = cfg, .g = guidance, .co = {p, q}, .k1 = k1, .k2 = k2,  \
+    .h2 = c_order >= 2 || p_order >= 3 ? h2 : nullptr, .h3 = c_order >= 3 ? h3 : nullptr,                                       \
+    .x_src = c_order >= 1 ? x_last : nullptr, .x_keep = x_keep_out
+#define FD_UNIPC_ORDERS .c_ord = c_order, .p_ord = p_order, .uc = {cx, cn, c1, c2, c3}, .up = {ax, w0, w1, w2}
+
+extern "C" int fd_cfg_unipc_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* m_out, const float* h1,
+                                     const float* h2, const float* h3, const float* x_last, float* x_keep_out, const float* z0,
+                                     const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg, float guidance,
+                                     int c_order, int p_order, float p, float q, float cx, float cn, float c1, float c2, float c3,
+                                     float ax, float w0, float w1, float w2, float k1, float k2, void* stream) {
+    FD_PLAN(fd_cfg_unipc_step_f32(x, eps_nhwc, eps_out, m_out, h1, h2, h3, x_last, x_keep_out, z0, noise, mask, B, C, HW, ld, cfg,
+                                  guidance, c_order, p_order, p, q, cx, cn, c1, c2, c3, ax, w0, w1, w2, k1, k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FdStepArgs s = {FD_UNIPC_FIELDS, FD_UNIPC_ORDERS};
+    return fd_step_run("fd_cfg_unipc_step_f32", FD_STEP_UNIPC, s, stream);
+}
+
+extern "C" int fd_cfg_rescale_unipc_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* m_out, const float* h1,
+                                             const float* h2, const float* h3, const float* x_last, float* x_keep_out,
+                                             float* scale_out, const float* z0, const float* noise, const float* mask, int B, int C,
+                                             int HW, int ld, float guidance, float rescale, int c_order, int p_order, float p,
+                                             float q, float cx, float cn, float c1, float c2, float c3, float ax, float w0, float w1,
+                                             float w2, float k1, float k2, void* stream) {
+    FD_PLAN(fd_cfg_rescale_unipc_step_f32(x, eps_nhwc, eps_out, m_out, h1, h2, h3, x_last, x_keep_out, scale_out, z0, noise, mask, B,
+                                          C, HW, ld, guidance, rescale, c_order, p_order, p, q, cx, cn, c1, c2, c3, ax, w0, w1, w2,
+                                          k1, k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    const int cfg = 1;
+    FdStepArgs s = {FD_UNIPC_FIELDS, FD_UNIPC_ORDERS};
+    const FdStepRescale rs = {rescale, scale_out};
+    return fd_step_run("fd_cfg_rescale_unipc_step_f32", FD_STEP_UNIPC, s, stream, 0, nullptr, &rs);
+}
+
+extern "C" int fd_composite_unipc_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities, float* eps_out,
+                                           float* m_out, const float* h1, const float* h2, const float* h3, const float* x_last,
+                                           float* x_keep_out, const float* z0, const float* noise, const float* mask, int B, int C,
+                                           int HW, int ld, int cfg, float guidance, int c_order, int p_order, float p, float q,
+                                           float cx, float cn, float c1, float c2, float c3, float ax, float w0, float w1, float w2,
+                                           float k1, float k2, void* stream) {
+    FD_PLAN(fd_composite_unipc_step_f32(x, eps_nhwc, weights, n_entities, eps_out, m_out, h1, h2, h3, x_last, x_keep_out, z0, noise,
+                                        mask, B, C, HW, ld, cfg, guidance, c_order, p_order, p, q, cx, cn, c1, c2, c3, ax, w0, w1,
+                                        w2, k1, k2, fd_s_));
+    FdProfScope fd_prof_(FD_FAMILY_OTHER, stream, 0.0, fd_tag(1u, __LINE__));
+    FdStepArgs s = {FD_UNIPC_FIELDS, .wmap = weights, .n_ent = n_entities, FD_UNIPC_ORDERS};
+    return fd_step_run("fd_composite_unipc_step_f32", FD_STEP_UNIPC, s, stream);
+}
+#undef FD_UNIPC_FIELDS
+#undef FD_UNIPC_ORDERS
 
 // One thread owns one Philox block: elements 4q..4q+3 of one sample, as far as the sample and the buffer reach.
 __global__ __launch_bounds__(256) void k_philox_normal(float* out, size_t n, const FdNoiseAddr a) {

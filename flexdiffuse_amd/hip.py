@@ -110,6 +110,10 @@ _SIGNATURES = {
                                         + [c_uint64, c_int64, c_int, c_int, P]),
     'fd_composite_linear_multistep_step_f32': (c_int, [P, P, P, c_int, c_int, c_int] + [P] * 10 + [c_int] * 5
                                                + [c_float] * 11 + [P]),
+    'fd_cfg_unipc_step_f32': (c_int, [P] * 12 + [c_int] * 5 + [c_float] + [c_int] * 2 + [c_float] * 13 + [P]),
+    'fd_cfg_rescale_unipc_step_f32': (c_int, [P] * 13 + [c_int] * 4 + [c_float] * 2 + [c_int] * 2 + [c_float] * 13 + [P]),
+    'fd_composite_unipc_step_f32': (c_int, [P] * 3 + [c_int] + [P] * 10 + [c_int] * 5 + [c_float] + [c_int] * 2
+                                    + [c_float] * 13 + [P]),
     'fd_lerp_f16': (c_int, [P, P, P, c_int64, c_float, P]),
     'fd_xattn_fold_rows_f32': (c_int, [P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P]),
     'fd_window_gather_f32': (c_int, [P, P] + [c_int] * 10 + [P]),

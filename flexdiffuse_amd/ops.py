@@ -1307,6 +1307,52 @@ def composite_linear_multistep_step(x: torch.Tensor, eps_nhwc: torch.Tensor, wei
                            form, hist, h_out, B, C, HW, cfg, guidance, weights, coef, mask, x_keep_out, x_src, x_scaled_out, scale)
 
 
+def _unipc_step(entry: str, x, eps_nhwc, entities, m_out, hist, x_last, x_keep_out, middle, B, C, HW, lead, orders, coef, mask,
+                eps_out):
+    '''The body of the UniPC fronts: `entities` the (weights, n) of the composite front, `middle` the scale_out of the rescaled
+    one (each () elsewhere), `lead` the ints and floats between ld and the orders.'''
+    z0, nz, mk, k1, k2 = _blend(mask, HW, B * C * HW)
+    hist = list(hist)
+    assert len(hist) <= 3 and len(coef) == 11 and len(orders) == 2, (len(hist), len(coef), orders)
+    _check_f32(B * C * HW, x, eps_out, m_out, x_last, x_keep_out, *hist)
+    hip.call(entry, x.data_ptr(), eps_nhwc.data_ptr(), *entities, _p(eps_out), _p(m_out), *([_p(t) for t in hist] + [None] * 3)[:3],
+             _p(x_last), _p(x_keep_out), *middle, _p(z0), _p(nz), _p(mk), B, C, HW, eps_nhwc.stride(0), *lead, int(orders[0]),
+             int(orders[1]), *_floats(coef, 11), k1, k2, hip.stream())
+
+
+def cfg_unipc_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m_out: torch.Tensor, hist, x_last: Optional[torch.Tensor],
+                   x_keep_out: torch.Tensor, B: int, C: int, HW: int, cfg: bool, guidance: float, orders, coef, mask=None,
+                   eps_out: Optional[torch.Tensor] = None):
+    '''UniPC step (fd_cfg_unipc_step_f32), in place on x (NCHW fp32): e = CFG(eps_nhwc) (-> eps_out when given);
+    m = p x + q e -> m_out; the corrector xc = cx x_last + cn m + sum c_k h_k at orders[0] (0: xc = x) -> x_keep_out (may be
+    x_last); the predictor x' = ax xc + w0 m + sum w_k h_k at orders[1]; `hist`: the earlier x0 rows, newest first (at most 3);
+    coef = (p, q, cx, cn, c1, c2, c3, ax, w0, w1, w2) of `UniPCMultistepScheduler.step_coefficients`; then the known-region
+    blend of mask = (z0, noise, mask [HW], k1, k2).'''
+    _guided_rows(eps_nhwc, None, B, C, HW, cfg)
+    _unipc_step('fd_cfg_unipc_step_f32', x, eps_nhwc, (), m_out, hist, x_last, x_keep_out, (), B, C, HW,
+                (int(cfg), float(guidance)), orders, coef, mask, eps_out)
+
+
+def cfg_rescale_unipc_step(x: torch.Tensor, eps_nhwc: torch.Tensor, m_out: torch.Tensor, hist, x_last: Optional[torch.Tensor],
+                           x_keep_out: torch.Tensor, B: int, C: int, HW: int, guidance: float, rescale: float, orders, coef,
+                           mask=None, eps_out: Optional[torch.Tensor] = None, scale_out: Optional[torch.Tensor] = None):
+    '''CFG + guidance rescale + UniPC step (fd_cfg_rescale_unipc_step_f32): `cfg_unipc_step` with CFG on and the guided output
+    rescaled as in `cfg_rescale_ddim_step` before m.  rescale == 0: its bits.'''
+    _guided_rows(eps_nhwc, None, B, C, HW, True)
+    _check_scale_out(scale_out, B, eps_nhwc)
+    _unipc_step('fd_cfg_rescale_unipc_step_f32', x, eps_nhwc, (), m_out, hist, x_last, x_keep_out, (_p(scale_out),), B, C, HW,
+                (float(guidance), float(rescale)), orders, coef, mask, eps_out)
+
+
+def composite_unipc_step(x: torch.Tensor, eps_nhwc: torch.Tensor, weights: Optional[torch.Tensor], m_out: torch.Tensor, hist,
+                         x_last: Optional[torch.Tensor], x_keep_out: torch.Tensor, B: int, C: int, HW: int, cfg: bool,
+                         guidance: float, orders, coef, mask=None, eps_out: Optional[torch.Tensor] = None):
+    '''CompositeGuide UniPC step (fd_composite_unipc_step_f32): `cfg_unipc_step` on the blend + CFG of `composite_step`'s rows
+    -- one launch.'''
+    _unipc_step('fd_composite_unipc_step_f32', x, eps_nhwc, _guided_rows(eps_nhwc, weights, B, C, HW, cfg), m_out, hist, x_last,
+                x_keep_out, (), B, C, HW, (int(cfg), float(guidance)), orders, coef, mask, eps_out)
+
+
 def window_gather(canvas: torch.Tensor, windows: torch.Tensor, B: int, C: int, grid):
     '''Canvas (B, C, H, W) -> window batch (B Wn, C, h, w), both NCHW fp32 (fd_window_gather_f32).  grid: the plain ints
     (H, W, h, w, stride_y, stride_x, ny, nx) of `windows.WindowGrid.args`; the kernel restates the offsets.'''

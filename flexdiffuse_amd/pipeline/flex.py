@@ -18,7 +18,7 @@ Which loop a request runs -- and which launch its step ends in -- is decided onc
 of every route is that module's docstring.  `__call__` is: argument checks, the first latents (`_init_latents`), the route, the
 request's state (`_begin`), and a loop that calls ONE step method per iteration (`_step_ddim`, `_step_multistep`, `_step_linear`,
 `_step_window`, `_step_generic`).  Beyond the reference, each on every route and with the same bits on all of them:
-  - DPM-Solver++ and its SDE form, PLMS and K-LMS on the device loop (`fuse_linear_multistep`), the step one launch after the UNet;
+  - DPM-Solver++ and its SDE form, UniPC, PLMS and K-LMS on the device loop (`fuse_linear_multistep`), the step one launch after the UNet;
   - composition under every scheduler (`fuse_composite`): the entity blend inside the step's one launch;
   - masked img2img (`mask_image=`; pipeline/inpaint.py): after every step the kept region of the latents is put back on the
     re-noised init latents, inside the step's own launch on the device loops, by one blend-only launch after the step elsewhere;
@@ -533,7 +533,8 @@ class FlexPipeline():
 
     def _step_multistep(self, s: _Request, i: int, t, latents):
         '''DPM-Solver++ and its SDE form on the device loop: the UNet, then the scheduler's one launch (CFG, x0, history,
-        multistep update, step noise, known-region blend), with the rescale or the entity blend ahead of it in that launch.'''
+        multistep update, step noise, known-region blend), with the rescale or the entity blend ahead of it in that launch.
+        UniPC (`unipc`): the same calls on its scheduler -- corrector, kept sample and predictor in that one launch, no noise.'''
         r, guide, B, C, HW = s.route, s.guide, s.B, s.C, s.H * s.W
         eps, latents = self._eps(s, latents, int(t), latents)
         blend, noise = s.mask(i), (s.step_noise, s.t_start + i) if r.sde else None
@@ -696,8 +697,8 @@ class FlexPipeline():
         if route.sde and step_noise is None:
             step_noise = PhiloxNoise(generator.initial_seed() if generator is not None else 0)
         s, latents = self._begin(route, guide, latents.contiguous(), t_start, known, eta, step_noise, debug, bridge)
-        step = {'ddim': self._step_ddim, 'multistep': self._step_multistep, 'linear': self._step_linear,
-                'window': self._step_window}.get(route.loop, self._step_generic)
+        step = {'ddim': self._step_ddim, 'multistep': self._step_multistep, 'unipc': self._step_multistep,
+                'linear': self._step_linear, 'window': self._step_window}.get(route.loop, self._step_generic)
         # a guide with a context schedule (ScheduledGuide, CompositeGuide(style_linear=)): told the GLOBAL step index at the top of
         # every iteration, on every route; guides without `at_step` run as before
         at_step = getattr(guide, 'at_step', None)

@@ -16,7 +16,8 @@ import torch
 import torch.nn.functional as F
 
 from ..encode.clip import sd_size
-from ..scheduler import DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler, PNDMScheduler
+from ..scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, LMSDiscreteScheduler, PNDMScheduler,
+                         UniPCMultistepScheduler)
 
 
 def _is_pil(obj: Any) -> bool:
@@ -75,7 +76,7 @@ def known_coefficients(scheduler, timesteps: Sequence, t_start: int,
     OUTPUT, known = k1 z0 + k2 n, from the scheduler's own tables.  DDIM: (sqrt(a_p), sqrt(1 - a_p))
     with the a_p of `_alphas(t)`; PNDM: the same with the a_p its `step` hands to
     `prev_coefficients` (index + 1 - offset; its second call lands on the level of its first);
-    K-LMS (sigma space, x = z0 + sigma n): (1, sigmas[i + 1]); DPM-Solver++: (alpha_t, sigma_t) of the step's target
+    K-LMS (sigma space, x = z0 + sigma n): (1, sigmas[i + 1]); DPM-Solver++ and UniPC: (alpha_t, sigma_t) of the step's target
     t = the next timestep of the list (its steps of either order keep a sample with eps = n on that level, and an img2img
     request starts on the table).  The last pair is (1, 0) exactly.
 
@@ -96,7 +97,7 @@ def known_coefficients(scheduler, timesteps: Sequence, t_start: int,
         for t in ts:
             a_p = scheduler._alphas(int(t))[1]
             pairs.append((float(np.sqrt(a_p)), float(np.sqrt(one - a_p))))
-    elif isinstance(scheduler, DPMSolverMultistepScheduler):
+    elif isinstance(scheduler, (DPMSolverMultistepScheduler, UniPCMultistepScheduler)):
         for i in range(len(ts)):
             t = int(ts[i + 1]) if i + 1 < len(ts) else 0
             pairs.append((float(np.float32(scheduler.alpha_t[t])), float(np.float32(scheduler.sigma_t[t]))))

@@ -20,6 +20,10 @@ gets one from the generator's seed).  The first row that applies is the route:
   fuse               DPM-Solver++ (2M), its SDE form       multistep       one launch: fd_cfg_multistep_step_f32 | _noise_ (SDE) |
                                                                            fd_cfg_rescale_multistep_step_f32 |
                                                                            fd_composite_multistep_step_f32
+  fuse               UniPC (eta = 0, no step noise)        unipc           one launch: fd_cfg_unipc_step_f32 |
+                                                                           fd_cfg_rescale_unipc_step_f32 |
+                                                                           fd_composite_unipc_step_f32 (corrector, kept sample and
+                                                                           predictor in it)
   fuse               PNDM, K-LMS; on, no rescale,          linear          one launch: fd_cfg_linear_multistep_step_f32 |
                      `fuse_linear_multistep`                               fd_composite_linear_multistep_step_f32 (K-LMS: the launch
                                                                            also writes the next scaled model input)
@@ -45,24 +49,25 @@ launch, fd_latent_upscale_noise_f32 (upscale + add_noise; the noise in-kernel wi
   any other          the canvas (windows_out = NULL)       the route's own setup, unchanged (the copy into the persistent buffer,
                                                            K-LMS's scaled input, `window_planned`'s gather)
 
-`ddim`, `multistep` and `linear` (PLMS) step in the persistent buffer the graph / plan reads when `on` (`persistent`); every
+`ddim`, `multistep`, `unipc` and `linear` (PLMS) step in the persistent buffer the graph / plan reads when `on` (`persistent`); every
 loop but `generic` reads the request's time-embedding table (`temb_table`).  Guidance rescale applies to a simple guide only
 (any other applies or ignores its own attribute in its `noise_pred`) and is refused for a window guide.  On `planned`,
 `window_planned` and `generic` a scheduler whose `step` takes `step_noise=` draws from the stream (`takes_noise`), one whose
-`step` takes `eta=` gets it (`accepts_eta`).'''
+`step` takes `eta=` gets it (`accepts_eta`).  UniPC has no stochastic form: `eta > 0` or `pipe.step_noise` under it is a ValueError
+on every route; its window guides run `window_planned` / `generic` through `scheduler.step`, the same kernel on B C planes.'''
 from __future__ import annotations
 
 import inspect
 from dataclasses import dataclass
 
 from ..scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, DPMSolverMultistepSDEScheduler, LMSDiscreteScheduler,
-                         PNDMScheduler)
+                         PNDMScheduler, UniPCMultistepScheduler)
 from .guide import SimpleGuide, WindowedGuide
 
 
 @dataclass(frozen=True)
 class Route():
-    loop: str               # 'ddim' | 'multistep' | 'linear' | 'window' | 'planned' | 'window_planned' | 'generic'
+    loop: str               # 'ddim' | 'multistep' | 'unipc' | 'linear' | 'window' | 'planned' | 'window_planned' | 'generic'
     guide: str              # 'simple' | 'composite' | 'window' | 'other'
     fuse_entities: bool     # composite: the entity blend inside the scheduler's own one-launch step
     noisy: bool             # DDIM's eta > 0 term from the counter-based stream, inside the step's launch
@@ -95,6 +100,9 @@ def select_route(guide, scheduler, unet, *, eta, step_noise, rescale, debug, use
     fuse = kind == 'simple' or fuse_entities
     ddim, multistep = isinstance(scheduler, DDIMScheduler), isinstance(scheduler, DPMSolverMultistepScheduler)
     sde, is_lms = isinstance(scheduler, DPMSolverMultistepSDEScheduler), isinstance(scheduler, LMSDiscreteScheduler)
+    unipc = isinstance(scheduler, UniPCMultistepScheduler)
+    if unipc and (eta or step_noise is not None):
+        raise ValueError('UniPCMultistepScheduler has no stochastic form: it takes neither eta > 0 nor pipe.step_noise')
     has_noise = step_noise is not None or sde
     on = bool(use_graph or use_plan) and not debug
     loop, noisy = 'generic', False
@@ -104,6 +112,8 @@ def select_route(guide, scheduler, unet, *, eta, step_noise, rescale, debug, use
             loop = 'ddim'
         elif multistep and fuse:
             loop = 'multistep'
+        elif unipc and fuse:
+            loop = 'unipc'
         elif on and fuse and not rescale and fuse_linear_multistep and isinstance(scheduler, (PNDMScheduler, LMSDiscreteScheduler)):
             loop = 'linear'
         else:
@@ -114,5 +124,5 @@ def select_route(guide, scheduler, unet, *, eta, step_noise, rescale, debug, use
     step = inspect.signature(scheduler.step).parameters
     return Route(loop, kind, fuse_entities, noisy, multistep, sde, is_lms, rescale,
                  takes_noise=has_noise and 'step_noise' in step, accepts_eta='eta' in step,
-                 persistent=on and (loop in ('ddim', 'multistep') or (loop == 'linear' and not is_lms)),
+                 persistent=on and (loop in ('ddim', 'multistep', 'unipc') or (loop == 'linear' and not is_lms)),
                  temb_table=loop != 'generic' and hasattr(unet, 'time_bias_table'))

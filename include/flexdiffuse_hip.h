@@ -645,6 +645,45 @@ int fd_composite_linear_multistep_step_f32(float* x, const float* eps_nhwc, cons
                                            const float* noise, const float* mask, int B, int C, int HW, int ld, int cfg,
                                            float guidance, float w0, float w1, float w2, float w3, float a0, float a1, float a2,
                                            float scale, float k1, float k2, void* stream);
+/* UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"; additive;
+ * FD_ABI_VERSION stays 12): the corrector of the previous step's sample and the predictor of the next one in ONE launch of
+ * k_latent_step (csrc/step.hip), with the coefficients of UniPCMultistepScheduler.step_coefficients.  x, eps_nhwc, z0, noise,
+ * mask, B, C, HW, ld, cfg, guidance, k1, k2 as fd_cfg_multistep_step_f32.  h1, h2, h3: the x0 rows of the earlier steps, newest
+ * first (NCHW fp32); x_last: the corrected sample the previous step's predictor started from.  Per element, every operation a
+ * separately rounded fp32 one, every sum in the order written:
+ *   e = the guided eps -> eps_out (optional, NCHW fp32)
+ *   m = p x + q e -> m_out                                          (x: the sample the model saw)
+ *   xc = cx x_last + cn m, then xc += c_k h_k for k = 1..c_order     (c_order == 0: no corrector, xc = x)
+ *   xc -> x_keep_out
+ *   x' = ax xc + w0 m, then x' += w_k h_k for k = 1..p_order - 1
+ *   the known-region blend (mask != NULL) -> x
+ * A row is read only at k <= max(c_order, p_order - 1) and x_last only with c_order >= 1; what is not read may be NULL, hold
+ * anything and have any alignment.  The kept sample is updated in place: x_keep_out may be x_last (a thread reads and writes
+ * only its own elements); no other output may be a buffer the launch reads or another output.  At c_order == 0 and
+ * p_order <= 2 the bits are fd_cfg_multistep_step_f32's on (p, q, ax, w0, w1).  FD_EINVAL before any launch: c_order outside
+ * 0..3, p_order outside 1..3, a NULL row at a used order, NULL x, eps_nhwc, m_out or x_keep_out, NULL x_last with a corrector,
+ * the aliasing above, the size and mask rules of the siblings. */
+int fd_cfg_unipc_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* m_out, const float* h1, const float* h2,
+                          const float* h3, const float* x_last, float* x_keep_out, const float* z0, const float* noise,
+                          const float* mask, int B, int C, int HW, int ld, int cfg, float guidance, int c_order, int p_order,
+                          float p, float q, float cx, float cn, float c1, float c2, float c3, float ax, float w0, float w1,
+                          float w2, float k1, float k2, void* stream);
+/* ... with guidance rescale (CFG implied; one workgroup per sample, as fd_cfg_rescale_multistep_step_f32): e = f_b e before m.
+ * rescale == 0: the bits of fd_cfg_unipc_step_f32 with cfg. */
+int fd_cfg_rescale_unipc_step_f32(float* x, const float* eps_nhwc, float* eps_out, float* m_out, const float* h1,
+                                  const float* h2, const float* h3, const float* x_last, float* x_keep_out, float* scale_out,
+                                  const float* z0, const float* noise, const float* mask, int B, int C, int HW, int ld,
+                                  float guidance, float rescale, int c_order, int p_order, float p, float q, float cx, float cn,
+                                  float c1, float c2, float c3, float ax, float w0, float w1, float w2, float k1, float k2,
+                                  void* stream);
+/* ... with the entity blend of the composite forms above as the source of e.  n_entities == 0: fd_cfg_unipc_step_f32's kernel
+ * and bits. */
+int fd_composite_unipc_step_f32(float* x, const float* eps_nhwc, const float* weights, int n_entities, float* eps_out,
+                                float* m_out, const float* h1, const float* h2, const float* h3, const float* x_last,
+                                float* x_keep_out, const float* z0, const float* noise, const float* mask, int B, int C, int HW,
+                                int ld, int cfg, float guidance, int c_order, int p_order, float p, float q, float cx, float cn,
+                                float c1, float c2, float c3, float ax, float w0, float w1, float w2, float k1, float k2,
+                                void* stream);
 /* Context schedules (additive; FD_ABI_VERSION stays 12): out[i] = half_rn(a[i] + w * (b[i] - a[i])) on contiguous fp16 buffers of n
  * elements -- the subtraction, the product and the sum three separately rounded fp32 operations (no FMA), one rounding to half.
  * w == 0 stores a's bits, w == 1 stores b's bits; a[i] == b[i] gives a[i] for every w (a zero of either sign: +0 unless w is 0 or 1).
