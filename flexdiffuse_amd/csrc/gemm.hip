@@ -1308,6 +1308,19 @@ static int gemm_check(const fd_gemm_desc* d, GemmArgs& g, int* batch_out) {
         g.KW = d->kw; g.stride = d->stride; g.pad_t = d->pad_t; g.pad_l = d->pad_l;
         g.up = d->upsample2x == 1;
         g.phase = d->upsample2x == 2;
+        // The loaders keep a row's first tap as two packed 16-bit halves -- (y + 16) << 16 | (x + 16) in the LDS-DMA kernels, (y + 0x4000) << 16 |
+        // (x + 0x4000) per DMA group in the ping-pong kernels -- and mark a row past M with y = 0xffff: every tap coordinate, -pad .. (out - 1) stride
+        // + k - 1 - pad, and the size of the view the bounds test measures against must stay inside what those hold.
+        {
+            const int upf = g.up ? 2 : 1;
+            FD_CHECK_ARG(d->upsample2x >= 0 && d->upsample2x <= 2 && d->stride >= 1 && d->kh >= 1 && d->kw >= 1 && d->pad_t >= 0 && d->pad_t <= 16 &&
+                             d->pad_l >= 0 && d->pad_l <= 16 && d->in_h >= 1 && d->in_w >= 1 && d->out_h >= 1 && d->out_w >= 1 &&
+                             (long long)d->in_h * upf <= 0x4000 && (long long)d->in_w * upf <= 0x4000 &&
+                             (long long)(d->out_h - 1) * d->stride + d->kh <= 0x4000 && (long long)(d->out_w - 1) * d->stride + d->kw <= 0x4000,
+                         FD_ESHAPE, "fd_gemm_f16: conv geometry outside the loaders' range: upsample2x 0..2, stride / kh / kw >= 1, pad_t / pad_l 0..16, "
+                                    "input view and (out - 1) * stride + k at most 16384 (got upsample2x=%d stride=%d k=%dx%d pad=(%d,%d) in=%dx%d out=%dx%d)",
+                         d->upsample2x, d->stride, d->kh, d->kw, d->pad_t, d->pad_l, d->in_h, d->in_w, d->out_h, d->out_w);
+        }
         FD_CHECK_ARG(d->in_c % BK == 0, FD_ESHAPE,
                      "fd_gemm_f16: conv needs Cin %% 64 == 0 (got %d); use fd_im2col_f16", d->in_c);
         // the input may be a column slice of a wider NHWC matrix (a skip tensor living in its concat buffer): lda = pixel stride

@@ -172,7 +172,9 @@ typedef struct fd_gemm_desc {
      * low-resolution input, one per output-pixel parity (py, px) = (z >> 1, z & 1) with batch = 4: W is [4][N][2*2*in_c]
      * (batch_stride_w = N * ldw), the 3x3 taps that fall on the same source pixel pre-summed per parity (4/9 of the MACs,
      * same sums); M = B * in_h * in_w rows of the low-resolution grid, out_h = in_h, out_w = in_w, kh = kw = 2, and C is the
-     * FULL-resolution [B][2 in_h][2 in_w][ldc] map into which slice z writes the pixels (2y + py, 2x + px). */
+     * FULL-resolution [B][2 in_h][2 in_w][ldc] map into which slice z writes the pixels (2y + py, 2x + px).
+     * Ranges (FD_ESHAPE outside them, before any launch): upsample2x 0..2; stride, kh, kw >= 1; pad_t, pad_l 0..16; the input view
+     * (in_h, in_w; doubled under upsample2x == 1) and (out - 1) * stride + k at most 16384 in each direction. */
     int32_t conv, in_h, in_w, in_c, out_h, out_w, kh, kw, stride, pad_t, pad_l, upsample2x;
     /* transposed store: C is [sample][N][trans_ld] (row n, column m within the sample) */
     int32_t trans_out, trans_ld;

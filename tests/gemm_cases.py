@@ -11,9 +11,10 @@ Every case forces its tile (fd_gemm_desc.tile) and split-K factor, so the rule c
 split come from fd_gemm_plan (host logic only), the rest of the launch -- epilogue, convolution form, transposed store,
 one-shot / persistent / register-staged kernel, finish kernel -- from `expected_launch`.
 
-Left out: FD_GEMM_PP (it only moves the rule, and the cases force their tiles), the fused / phase-decomposed upsample
-convolutions (upsample2x; tests/test_gpu_kernels.py::test_upsample_conv_phase_decomposition), the experimental sk_sync, gn_skip_c
-and operands >= 2 GiB (the only way to the register-staged kernel besides FD_GEMM_NO_DMA).'''
+Left out: FD_GEMM_PP (it only moves the rule, and the cases force their tiles), the experimental sk_sync, gn_skip_c and operands
+>= 2 GiB (the only way to the register-staged kernel besides FD_GEMM_NO_DMA).  Every convolution of THIS table has one geometry --
+stride 1, padding (k - 1) // 2, a near-square output; the strided, unpadded, odd-sized, fused-upsample and phase-decomposed
+(upsample2x) geometries on every loader, the ping-pong tiles among them, are the table of tests/conv_cases.py, built on this module.'''
 from __future__ import annotations
 
 import ctypes
@@ -43,6 +44,8 @@ LEAN = {9: (128, 160, 4, 2, 2, 38), 10: (128, 128, 4, 2, 2, 110), 12: (128, 160,
         20: (128, 160, 4, 3, 2, 294)}
 GENERIC = {1: (128, 128, 2, 2, 2), 2: (128, 160, 2, 2, 2), 3: (128, 64, 2, 2, 2), 4: (64, 64, 2, 2, 2), 5: (256, 160, 4, 2, 2),
            6: (256, 128, 4, 2, 2), 7: (256, 160, 4, 3, 2), 8: (256, 128, 4, 3, 2), 11: (128, 64, 4, 2, 2)}
+# (BM, BN, WM, WN) of the ping-pong tiles of csrc/gemm_pp.hip (fd_gemm_pp_tile_shape); tests/conv_cases.py forces them, no case of this table does
+PP = {30: (256, 320, 2, 4), 31: (256, 256, 2, 4), 32: (128, 320, 2, 4), 33: (256, 160, 4, 2)}
 
 
 class Case(NamedTuple):
@@ -61,7 +64,7 @@ class Case(NamedTuple):
     out_f32: bool = False
     batch: int = 1            # > 1: gapped batch strides
     batch_bias: bool = False
-    conv: Optional[tuple] = None     # (out_h, out_w, in_c, kh, kw, stride); pad = ((kh - 1) // 2, (kw - 1) // 2)
+    conv: Optional[tuple] = None     # (out_h, out_w, in_c, kh, kw, stride[, pad_t, pad_l[, upsample2x[, in_h, in_w]]]): see `geom`
     K2: int = 0
     ln: int = 0               # LayerNorm fold: 1 = finished statistics, 2 / 4 / 8 = ln_stats_parts
     stats_out: bool = False
@@ -79,6 +82,14 @@ class Case(NamedTuple):
     @property
     def rows(self) -> int:    # rows per sample as the kernel sees them
         return self.rps if self.rps > 0 else self.M
+
+    @property
+    def geom(self):
+        return geom(self.conv)
+
+    @property
+    def phase(self) -> bool:  # upsample2x == 2: batch = the four output parities, one shared input, one interleaved output
+        return self.conv is not None and self.geom.up == 2
 
     @property
     def edges(self) -> set:
@@ -103,6 +114,19 @@ class Case(NamedTuple):
 
 EDGES = ('padded', 'k_tail', 'ragged', 'alpha', 'batch', 'batch_bias', 'res_wrap', 'bias2', 'trans_pad')
 
+Geom = namedtuple('Geom', 'ho wo cin kh kw stride pad_t pad_l up hi wi')
+
+
+def geom(conv: tuple) -> Geom:
+    '''Case.conv with its defaults filled in: padding ((kh - 1) // 2, (kw - 1) // 2), upsample2x 0 (1: the loader reads a nearest-2x upsampled
+    view of the input; 2: the phase-decomposed form, four 2x2 parity filters over the low-resolution input) and an input of out * stride
+    (`hi`, `wi`: the size of the stored input; with upsample2x == 1 the loader's bounds are twice that).'''
+    ho, wo, cin, kh, kw, stride = conv[:6]
+    pad_t, pad_l = conv[6:8] if len(conv) >= 8 else ((kh - 1) // 2, (kw - 1) // 2)
+    up = conv[8] if len(conv) >= 9 else 0
+    hi, wi = conv[9:11] if len(conv) >= 11 else (ho * stride, wo * stride)
+    return Geom(ho, wo, cin, kh, kw, stride, pad_t, pad_l, up, hi, wi)
+
 
 # ------------------------------------------------------------------------------------------------ the launch, restated
 Launch = namedtuple('Launch', 'kernel tpl form finish tap_fast')
@@ -124,7 +148,7 @@ def launch_mode(g, split, env, BM, BN, TRANS, CONV, WM=2, NS=2, WN=2, EPI=0):
         nkt = _cdiv(g.K, BK) // split
         mode = int(env.get('FD_GEMM_PERSIST', 1))
         tiles = _cdiv(g.M, BM) * _cdiv(g.N, BN)
-        persistent = (NS == 2 and BN != 320 and EPI != 13 and g.K2 == 0 and not g.stats_out and g.ln_parts <= 1 and not g.stride_bias and
+        persistent = (NS == 2 and BN != 320 and EPI != 13 and g.K2 == 0 and not getattr(g, 'phase', False) and not g.stats_out and g.ln_parts <= 1 and not g.stride_bias and
                       (mode == 2 or (mode == 1 and nkt <= 20 and tiles > slots)))
         if 1 <= EPI <= 3 and persistent and g.bias2:
             return launch_mode(g, split, env, BM, BN, TRANS, CONV, WM, NS, WN, 0)
@@ -202,6 +226,31 @@ def select(g, tile, split, env={}) -> Launch:
         raise ValueError('gn_part_out needs the lean epilogue')
     if g.gn_out and split not in (2, 4, 8, 16):
         raise ValueError('gn_out is honoured by split-K launches only')
+    up, phase = getattr(g, 'up', False), getattr(g, 'phase', False)
+    if phase:
+        # gemm_check: only the lean plain epilogue knows the parity row map; gemm_check_tile: a tile that has one, full tiles, no split
+        if not lean_ok:
+            raise ValueError('upsample2x == 2 needs the lean epilogue on the LDS-DMA path')
+        bm, bn = LEAN[tile][:2] if tile in LEAN else PP[tile][:2] if tile in PP else (0, 0)
+        if not bm or g.M % bm or g.N % bn or split != 1:
+            raise ValueError('upsample2x == 2 needs full tiles of a tile with a lean epilogue and no split-K')
+    finish = None
+    if split > 1:
+        finish = f'k_splitk_finish_gn<{split}>' if g.gn_out else 'k_splitk_finish'
+    if tile in PP:
+        # fd_gemm_pp_ok / pp_launch of csrc/gemm_pp.hip, as far as the convolution table goes (plain, residual and per-sample-bias epilogues;
+        # the forced tile runs whatever FD_GEMM_PERSIST / FD_GEMM_NO_DMA / FD_CONV_TAPFAST say: one kernel, tap-fastest only)
+        BM, BN, WM, WN = PP[tile]
+        assert g.act == ACT_NONE and not (g.ln or g.stats_out or g.gn_part or g.gn_out or g.K2 or g.trans), 'not restated for the ping-pong tiles'
+        if g.M % BM or g.N % BN or g.K % BK:
+            raise ValueError('ping-pong tiles need full tiles and K % 64 == 0')
+        if g.conv and (g.Wo % 8 or up):
+            raise ValueError('ping-pong tiles: an 8-row DMA group is 8 consecutive pixels of one output row; no fused upsample')
+        if split > 1 and g.K // BK // split < 2:
+            raise ValueError('ping-pong tiles need two K-tiles per slice')
+        lean = split == 1 and not g.out_f32 and int(env.get('FD_GEMM_BIAS_LDS', 1)) != 0 and g.ldc % 8 == 0 and (not g.bias2 or g.rows % BM == 0)
+        epi = 10 if split > 1 and g.N % 4 == 0 else 2 if lean and g.res and g.ldr % 4 == 0 else 1 if lean and not g.res else 0
+        return Launch('k_gemm_f16_pp', (BM, BN, WM, 2, WN, epi, g.conv, False), 'pp', finish, bool(g.conv))
     tap_fast = g.conv and (int(env.get('FD_CONV_TAPFAST', 1)) == 2 or (int(env.get('FD_CONV_TAPFAST', 1)) == 1 and tile == 16))
     if g.ln and tile not in LEAN:
         # small problems: the generic epilogue with the fold compiled in (64x64 for few rows); fd_gemm_plan says 4 or -7
@@ -211,9 +260,6 @@ def select(g, tile, split, env={}) -> Launch:
     else:
         BM, BN, WM, NS, WN = GENERIC.get(tile, GENERIC[1])
         lm = launch_mode(g, split, env, BM, BN, False, g.conv, WM, NS, WN, 0)
-    finish = None
-    if split > 1:
-        finish = f'k_splitk_finish_gn<{split}>' if g.gn_out else 'k_splitk_finish'
     return Launch(*lm, finish, bool(tap_fast))
 
 
@@ -222,7 +268,8 @@ def flags(case: Case) -> SimpleNamespace:
     return SimpleNamespace(M=case.M, N=case.N, K=case.K, K2=case.K2, act=case.act, res=case.res, ldr=p['ldr'], ldc=p['ldc'], bias=True,
                            bias2=case.bias2, rows=case.rows, out_f32=case.out_f32, trans=case.trans, trans_n0=case.trans_n0, conv=case.conv is not None,
                            ln=case.ln > 0, ln_parts=case.ln if case.ln > 1 else 0, stats_out=case.stats_out, gn_part=case.gn_parts > 0,
-                           gn_out=case.gn_out > 0, stride_bias=case.batch_bias, batch=case.batch)
+                           gn_out=case.gn_out > 0, stride_bias=case.batch_bias, batch=case.batch,
+                           up=case.conv is not None and case.geom.up == 1, phase=case.phase, Wo=case.geom.wo if case.conv else 0)
 
 
 _plan_cache = {}
@@ -264,7 +311,8 @@ def launch_of_desc(d, env={}) -> Launch:
     g = SimpleNamespace(M=d.M, N=d.N, K=d.K, K2=d.K2, act=d.act, res=bool(d.residual), ldr=d.ldr, ldc=d.ldc, bias=bool(d.bias), bias2=bool(d.bias2),
                         rows=d.rows_per_sample if d.rows_per_sample > 0 else d.M, out_f32=bool(d.out_f32), trans=bool(d.trans_out), trans_n0=d.trans_n0,
                         conv=bool(d.conv), ln=bool(d.ln_stats), ln_parts=d.ln_stats_parts if d.ln_stats_parts > 1 else 0, stats_out=bool(d.ln_stats_out),
-                        gn_part=bool(d.gn_part_out), gn_out=bool(d.gn_out), stride_bias=bool(d.batch_stride_bias), batch=max(d.batch, 1))
+                        gn_part=bool(d.gn_part_out), gn_out=bool(d.gn_out), stride_bias=bool(d.batch_stride_bias), batch=max(d.batch, 1),
+                        up=bool(d.conv) and d.upsample2x == 1, phase=bool(d.conv) and d.upsample2x == 2, Wo=d.out_w)
     return select(g, tile.value, split.value, env)
 
 
@@ -293,9 +341,9 @@ def layout_plan(case: Case) -> dict:
     M, N, K, K2, n_out = case.M, case.N, case.K, case.K2, case.n_out
     p = {}
     if case.conv:
-        ho, wo, cin, kh, kw, stride = case.conv
+        ho, wo, cin, kh, kw = case.geom[:5]
         assert K == kh * kw * cin and M % (ho * wo) == 0 and cin % BK == 0
-        p['B'], p['Hi'], p['Wi'] = M // (ho * wo), ho * stride, wo * stride
+        p['B'], p['Hi'], p['Wi'] = M // (ho * wo), case.geom.hi, case.geom.wi
         p['lda'] = cin + 8 if pad else cin            # pixel stride
         p['a_size'] = p['B'] * p['Hi'] * p['Wi'] * p['lda']
     else:
@@ -315,7 +363,7 @@ def layout_plan(case: Case) -> dict:
         p['c_len'] = (M // case.rows) * p['sT']
         p['ldc'] = 0
     else:
-        p['c_len'] = M * p['ldc']
+        p['c_len'] = (4 * M if case.phase else M) * p['ldc']      # phase: [B][2 out_h][2 out_w] pixels, the four parities interleaved
     if case.trans_n0:
         p['ldt'] = case.rows + (8 if pad else 0)
         p['sT'] = (N - case.trans_n0) * p['ldt'] + (16 if pad else 0)
@@ -327,6 +375,12 @@ def layout_plan(case: Case) -> dict:
     p['sC'] = p['c_len'] + (GUARD_ROWS * p['ldc'] if gap and not case.stats_out else 0)
     p['sR'] = M * p['ldr'] + (32 if gap else 0)
     p['sBias'] = _r(N, 4) + 4 if case.batch_bias else 0
+    p['ZA'] = p['ZC'] = case.batch
+    if case.phase:
+        # the four parity slices read one input and write one output: batch_stride_a = batch_stride_c = 0, only W has a batch stride
+        assert case.batch == 4 and not case.res and not case.batch_bias
+        p['sA'] = p['sC'] = p['sR'] = 0
+        p['ZA'] = p['ZC'] = 1
     p['guard'] = GUARD_ROWS * max(p['ldc'], 8)
     return p
 
@@ -348,9 +402,9 @@ def build_desc(case: Case, p: dict, ptr: dict):
     if case.bias2:
         d.bias2, d.ld_bias2 = ptr['bias2'], p['ldb2']
     if case.conv:
-        ho, wo, cin, kh, kw, stride = case.conv
-        d.conv, d.in_h, d.in_w, d.in_c, d.out_h, d.out_w = 1, p['Hi'], p['Wi'], cin, ho, wo
-        d.kh, d.kw, d.stride, d.pad_t, d.pad_l = kh, kw, stride, (kh - 1) // 2, (kw - 1) // 2
+        q = case.geom
+        d.conv, d.in_h, d.in_w, d.in_c, d.out_h, d.out_w = 1, p['Hi'], p['Wi'], q.cin, q.ho, q.wo
+        d.kh, d.kw, d.stride, d.pad_t, d.pad_l, d.upsample2x = q.kh, q.kw, q.stride, q.pad_t, q.pad_l, q.up
     if case.K2:
         d.A2, d.lda2, d.K2 = ptr['A2'], p['lda2'], case.K2
     if case.ln:
@@ -391,7 +445,7 @@ def inputs(case: Case) -> dict:
     inp = {}
     if case.conv:
         cin = case.conv[2]
-        a = _rnd((Z, p['B'], p['Hi'], p['Wi'], cin), s)
+        a = _rnd((p['ZA'], p['B'], p['Hi'], p['Wi'], cin), s)
     else:
         a = _rnd((Z, M, K), s)
         if case.ln or case.stats_out:
@@ -440,15 +494,45 @@ def inputs(case: Case) -> dict:
     return inp
 
 
-def im2col(case: Case, a):
-    '''[B][Hi][Wi][Cin] -> [M][kh * kw * Cin] in the weights' (kh, kw, Cin) order, zero padding.'''
-    ho, wo, cin, kh, kw, stride = case.conv
-    pt, pl = (kh - 1) // 2, (kw - 1) // 2
-    B, Hi, Wi, _ = a.shape
-    ap = torch.zeros((B, Hi + 2 * pt + stride, Wi + 2 * pl + stride, cin), dtype=a.dtype)
-    ap[:, pt:pt + Hi, pl:pl + Wi] = a
-    cols = [ap[:, ky:ky + stride * ho:stride, kx:kx + stride * wo:stride] for ky in range(kh) for kx in range(kw)]
-    return torch.cat(cols, dim=-1).reshape(B * ho * wo, kh * kw * cin)
+def conv_taps(case: Case, z: int = 0, wrong: Optional[str] = None, bm: int = 0):
+    '''The loaders' geometry, restated: -> [M][kh * kw] int64, the linear pixel index (b * Hi + y) * Wi + x of the stored input that GEMM
+    row m = (b, oy, ox) reads for filter tap (ky, kx), -1 where the tap reads zero.  In the view the loader walks -- the stored input, or
+    its nearest-2x upsampling with upsample2x == 1 -- the tap is at (oy * stride - pad_t + ky, ox * stride - pad_l + kx); outside the view it
+    is zero; upsample2x == 1 halves the coordinates (>> 1).  upsample2x == 2: slice z = 2 py + px has pad (1 - py, 1 - px).
+    `wrong`: one of the wrong geometries of tests/conv_cases.py (`bm`: the tile's rows, for 'sample_base').'''
+    q = case.geom
+    hw, total = q.ho * q.wo, (case.M // (q.ho * q.wo)) * q.hi * q.wi
+    m = torch.arange(case.M)
+    b, rem = m // hw, m % hw
+    if wrong == 'sample_base':
+        b = (m // bm * bm) // hw
+    oy, ox = rem // q.wo, rem % q.wo
+    pt, pl = (1 - (z >> 1), 1 - (z & 1)) if q.up == 2 and wrong != 'phase_pad' else (q.pad_t, q.pad_l)
+    if wrong == 'pad_sym':
+        pt = pl = 1
+    if wrong == 'pad_swap':
+        pt, pl = pl, pt
+    stride = 1 if wrong == 'stride_one' else q.stride
+    ky, kx = torch.arange(q.kh).repeat_interleave(q.kw), torch.arange(q.kw).repeat(q.kh)
+    if wrong == 'tap_transpose':
+        ky, kx = kx, ky
+    iy, ix = (oy * stride - pt)[:, None] + ky[None, :], (ox * stride - pl)[:, None] + kx[None, :]
+    up = q.up == 1
+    hv, wv = (2 * q.hi, 2 * q.wi) if up and wrong != 'up_bounds_low' else (q.hi, q.wi)
+    ok_y, ok_x = (iy >= 0) & (iy < hv), (ix >= 0) & (ix < wv)
+    if up:
+        r = 1 if wrong == 'up_ceil' else 0
+        iy, ix = (iy + r) >> 1, (ix + r) >> 1
+    lin = (b[:, None] * q.hi * q.wi + iy * q.hi + ix) if wrong == 'hw_swap' else ((b[:, None] * q.hi + iy) * q.wi + ix)
+    ok = (ok_y & (lin >= 0) & (lin < total)) if wrong == 'edge_wrap' else (ok_y & ok_x)
+    return torch.where(ok, lin % total, torch.full_like(lin, -1))
+
+
+def im2col(case: Case, a, z: int = 0, wrong: Optional[str] = None, bm: int = 0):
+    '''[B][Hi][Wi][Cin] -> [M][kh * kw * Cin] in the weights' (kh, kw, Cin) order, zero padding: a gather through `conv_taps`.'''
+    cin = a.shape[-1]
+    flat = torch.cat([a.reshape(-1, cin), torch.zeros((1, cin), dtype=a.dtype)])       # (index -1: the zero pixel)
+    return flat[conv_taps(case, z, wrong, bm)].reshape(case.M, -1)
 
 
 # ------------------------------------------------------------------------------------------------ reference, emulation, mutants
@@ -494,10 +578,37 @@ def _matmul(a, w, dtype):
     return acc
 
 
-def compute(case: Case, inp: dict, dtype=torch.float64, mutant: Optional[str] = None, cache: Optional[dict] = None) -> Optional[dict]:
+def phase_rows(case: Case, z: int, wrong: Optional[str] = None):
+    '''upsample2x == 2: the output row (pixel of the [B][2 out_h][2 out_w] map) of every GEMM row m = (b, y, x) of parity slice z = 2 py + px:
+    pixel (2 y + py, 2 x + px).  `wrong`: 'phase_parity_swap' | 'phase_row_pitch' of tests/conv_cases.py.'''
+    q = case.geom
+    m = torch.arange(case.M)
+    b, rem = m // (q.ho * q.wo), m % (q.ho * q.wo)
+    py, px = (z & 1, z >> 1) if wrong == 'phase_parity_swap' else (z >> 1, z & 1)
+    return (b * 2 * q.ho + 2 * (rem // q.wo) + py) * ((1 if wrong == 'phase_row_pitch' else 2) * q.wo) + 2 * (rem % q.wo) + px
+
+
+def phase_store(case: Case, y4, wrong: Optional[str] = None):
+    '''[4][M][N] -> [1][4 M][N]: the interleaved store of the four parity slices (an element no slice writes keeps the sentinel).'''
+    out = torch.full((1, 4 * case.M, y4.shape[-1]), SENTINEL, dtype=y4.dtype)
+    for z in range(4):
+        out[0, phase_rows(case, z, wrong)] = y4[z]
+    return out
+
+
+def phase_slices(case: Case, c):
+    '''The inverse of `phase_store`: [1][4 M][N] -> [4][M][N].'''
+    return torch.stack([c[0, phase_rows(case, z)] for z in range(4)])
+
+
+def compute(case: Case, inp: dict, dtype=torch.float64, mutant: Optional[str] = None, cache: Optional[dict] = None, acc_of=None,
+            store_wrong: Optional[str] = None) -> Optional[dict]:
     '''The operation of `case` on the rounded operands in `dtype` (float64: the reference; float32: the emulation, output rounded like the
-    device's) -> {'C': [batch][M][n_out] (transposed store: [batch][samples][N][rows]), 'C2'}; None where the mutant does not apply.
-    `cache`: a dict of the caller's that keeps the accumulators (never modified here) between the mutants of one case.'''
+    device's) -> {'C': [batch][M][n_out] (transposed store: [batch][samples][N][rows]; upsample2x == 2: [1][4 M][n_out]), 'C2'}; None where
+    the mutant does not apply.
+    `cache`: a dict of the caller's that keeps the accumulators (never modified here) between the mutants of one case.
+    `acc_of(z)`: the [M][N] accumulator of batch z from elsewhere (tests/conv_cases.py: F.conv2d for the reference, a wrong geometry for a
+    mutant) in place of im2col + matmul; `store_wrong`: a wrong parity store (`phase_rows`).'''
     assert mutant is None or mutant in MUTANTS
     if mutant is not None and not applies(case, mutant):
         return None
@@ -508,8 +619,10 @@ def compute(case: Case, inp: dict, dtype=torch.float64, mutant: Optional[str] = 
     outs = []
     for z in range(case.batch):
         key = (dtype, z, mutant == 'k_chunk')
+        if acc_of is not None:
+            cache = {key: acc_of(z)}
         if cache is None or key not in cache:
-            a = im2col(case, inp['A'][z]) if case.conv else inp['A'][z]
+            a = im2col(case, inp['A'][0 if case.phase else z], z) if case.conv else inp['A'][z]
             if case.K2:
                 a = torch.cat([a, inp['A2']], dim=1)
             if mutant == 'k_chunk':
@@ -565,6 +678,8 @@ def compute(case: Case, inp: dict, dtype=torch.float64, mutant: Optional[str] = 
         outs.append(y)
     y = torch.stack(outs)
     out = {}
+    if case.phase:
+        return {'C': phase_store(case, y, store_wrong)}
     if mutant == 'tile_swap':
         bm, bn = expected_launch(case).tpl[:2]
         bn = bn // 2 if case.act == ACT_GEGLU else bn
@@ -625,6 +740,8 @@ def tile_liveness(case: Case, want: dict) -> float:
         y = want['C'].transpose(2, 3).reshape(case.batch, case.M, case.N)
     elif case.trans_n0:
         y = torch.cat([want['C'], want['C2'].transpose(1, 2).reshape(1, case.M, -1)], dim=2)
+    elif case.phase:
+        y = phase_slices(case, want['C'])
     else:
         y = want['C']
     live = (y.abs() >= LIVE_ABS).double()
@@ -722,10 +839,12 @@ def host_buffers(case: Case, inp: dict) -> dict:
     '''Flat host buffers of the case's layout: junk (PAD_IN) in every input padding, SENTINEL in every output element.'''
     p, Z, M, N = layout_plan(case), case.batch, case.M, case.N
     h = {}
-    a = torch.full((Z * p['sA'],), PAD_IN, dtype=torch.float16)
+    a = torch.full((max(Z * p['sA'], p['a_size']),), PAD_IN, dtype=torch.float16)
     w = torch.full((Z * p['sW'],), PAD_IN, dtype=torch.float16)
     for z in range(Z):
-        if case.conv:
+        if case.conv and z >= p['ZA']:
+            pass
+        elif case.conv:
             t = inp['A'][z]
             torch.as_strided(a, tuple(t.shape), (p['Hi'] * p['Wi'] * p['lda'], p['Wi'] * p['lda'], p['lda'], 1), z * p['sA']).copy_(t)
         else:
@@ -752,7 +871,7 @@ def host_buffers(case: Case, inp: dict) -> dict:
         if k in inp:
             h[k] = inp[k]
     cdt = torch.float32 if case.out_f32 else torch.float16
-    h['C'] = torch.full((2 * p['guard'] + (Z - 1) * p['sC'] + p['c_len'],), SENTINEL, dtype=cdt)
+    h['C'] = torch.full((2 * p['guard'] + (p['ZC'] - 1) * p['sC'] + p['c_len'],), SENTINEL, dtype=cdt)
     if case.trans_n0:
         h['C2'] = torch.full((p['c2_len'] + 16,), SENTINEL, dtype=torch.float16)
     if case.stats_out:
@@ -773,6 +892,8 @@ def _views(case: Case, p: dict, back: dict) -> dict:
     v = {}
     if case.trans:
         v['C'] = torch.as_strided(back['C'], (Z, ns, case.N, case.rows), (p['sC'], p['sT'], p['ldt'], 1), p['guard'])
+    elif case.phase:
+        v['C'] = torch.as_strided(back['C'], (1, 4 * M, case.n_out), (0, p['ldc'], 1), p['guard'])
     else:
         v['C'] = torch.as_strided(back['C'], (Z, M, case.trans_n0 if case.trans_n0 else case.n_out), (p['sC'], p['ldc'], 1), p['guard'])
     if case.trans_n0:
@@ -815,11 +936,12 @@ def run_on_device(case: Case, dev, inp: Optional[dict] = None):
     return out, bool(untouched)
 
 
-def run_and_score(case: Case, dev, env={}):
-    '''-> one result row: the expected kernel, err / bound of the outputs and of the statistics, untouched.'''
+def run_and_score(case: Case, dev, env={}, ref=None):
+    '''-> one result row: the expected kernel, err / bound of the outputs and of the statistics, untouched.  `ref`: another float64 reference
+    than `reference` (tests/conv_cases.py: torch.nn.functional.conv2d).'''
     inp = inputs(case)
     got, untouched = run_on_device(case, dev, inp)
-    want = reference(case, inp)
+    want = (ref or reference)(case, inp)
     ratio = worst(case, got, want)
     sratio = 0.0
     if case.stats_out or case.gn_parts:
@@ -1052,10 +1174,11 @@ BY_ID = {c.id: c for c in CASES}
 assert len(BY_ID) == len(CASES), 'case ids must be unique'
 
 
-def child_cases(env: dict):
-    '''The cases a child process under `env` runs: those the library still accepts whose expected launch the setting changes.'''
+def child_cases(env: dict, cases=None):
+    '''The cases (of `cases`; default: this table) a child process under `env` runs: those the library still accepts whose expected launch
+    the setting changes.'''
     run, skipped = [], []
-    for c in CASES:
+    for c in (CASES if cases is None else cases):
         if refused(c):
             continue
         if refused(c, env):
@@ -1065,11 +1188,12 @@ def child_cases(env: dict):
     return run, skipped
 
 
-def _child(job: dict) -> int:
+def _child(job: dict, by_id: Optional[dict] = None, ref=None) -> int:
     """Runs, in THIS fresh process (the switches are read once per process), the cases the parent names: job = {'env', 'run': ids whose launch
     the setting changes, 'refuse': ids the setting makes the library refuse (ValueError, each followed by the good call 'good': an id of
     'run')}; one JSON line on stdout.
-    (The parent decides, with fd_gemm_plan under the default settings; here fd_gemm_plan itself runs under the setting.)"""
+    (The parent decides, with fd_gemm_plan under the default settings; here fd_gemm_plan itself runs under the setting.)
+    `by_id`, `ref`: the table and reference of tests/conv_cases.py, whose own --child entry ends up here."""
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     if root not in sys.path:
         sys.path.insert(0, root)
@@ -1077,16 +1201,17 @@ def _child(job: dict) -> int:
     for name, value in env.items():
         assert os.environ.get(name) == value, f'{name} must be set in the child environment'
     dev = torch.device('cuda:0')
+    by_id = by_id if by_id is not None else BY_ID
     rows, refusals = [], []
-    for c in (BY_ID[i] for i in job['refuse']):
+    for c in (by_id[i] for i in job['refuse']):
         try:
             run_on_device(c, dev)
             refusals.append({'id': c.id, 'refused': False})
         except ValueError:
             refusals.append({'id': c.id, 'refused': True})
-        refusals[-1]['good_after'] = run_and_score(BY_ID[job['good']], dev, env)['ok']
-    for c in (BY_ID[i] for i in job['run']):
-        rows.append(run_and_score(c, dev, env))      # (fd_gemm_plan under the setting must not refuse what `select` accepts: ValueError here)
+        refusals[-1]['good_after'] = run_and_score(by_id[job['good']], dev, env, ref)['ok']
+    for c in (by_id[i] for i in job['run']):
+        rows.append(run_and_score(c, dev, env, ref))      # (fd_gemm_plan under the setting must not refuse what `select` accepts: ValueError here)
     print(json.dumps({'env': env, 'cases': rows, 'refusals': refusals}), flush=True)
     return 0
 
