@@ -279,7 +279,7 @@ __global__ __launch_bounds__(64 * NW, (DQK <= 96 ? 2 : 1)) void k_attention(Attn
 
 
 // ---------------------------------------------------------------------------------------
-// 8-wave / 16-queries-per-wave variant with a VALU-lean softmax.  PMC on the N=4096 d=40
+// 8-wave variant (one or two 16-query blocks per wave) with a VALU-lean softmax.  PMC on the N=4096 d=40
 // self-attention showed the original loop VALU-issue-bound (7.4 VALU instructions per score,
 // VALU busy ~80 %, MFMA pipe 30 %), so this one removes per-score work:
 //  * LAZY running max: scores are exponentiated against a max that is only advanced when some
@@ -293,19 +293,34 @@ __global__ __launch_bounds__(64 * NW, (DQK <= 96 ? 2 : 1)) void k_attention(Attn
 //    also produces the softmax denominator (from the same fp16 P): no row-sum adds.
 //  * K / V^T tile loads are buffer loads (constant per-thread offsets, zero fill by the
 //    bounds check) instead of per-tile 64-bit address math.
+//
+// QB = 16-query blocks per wave: 1 (128 queries per workgroup) or 2 (256), the same arithmetic
+// per query.  On this chip the instructions of a SIMD's waves ADD UP (tools/micro/pipe_overlap.hip:
+// no overlap between v_mfma_f32_16x16x32 and VALU / DS issue), so the tile loop is bound by its
+// instruction count per score.  With QB = 2 both query blocks share every K and V^T fragment
+// read and the K / V^T tile staging: DS instructions and global loads per score halve; MFMA, exp
+// and convert counts per score are unchanged.  ~125 VGPRs (4 waves per SIMD: the kernel is not
+// sensitive to occupancy, tools/ab_attn_occ.py).
 #define LAZY_THR 8.0f
-#ifndef ATT_VPRE
-#define ATT_VPRE 0
-#endif
-#ifndef ATT_SETPRIO
-#define ATT_SETPRIO 0   // s_setprio(1) around the MFMA clusters of k_attention_w8q2 (measured: see profiles)
-#endif
+// The statements once per query block t of the wave.  With one block they stand alone, not in a `for` of one pass:
+// that `for` reaches the optimizer as a loop, and every QB = 1 kernel then comes out up to 27 instructions longer (the
+// lazy-max advance loses its packed multiplies) than the same statements on scalars.
+#define ATT_EACH_BLOCK(...)                                                                   \
+    if constexpr (QB == 1) {                                                                  \
+        constexpr int t = 0;                                                                  \
+        __VA_ARGS__                                                                           \
+    } else {                                                                                  \
+        _Pragma("unroll") for (int t = 0; t < QB; ++t) { __VA_ARGS__ }                        \
+    }
 #ifndef ATT_W8_MINW
-#define ATT_W8_MINW 8   // waves per SIMD the d <= 48 kernel is compiled for (8: 64 VGPRs, 6: 80 VGPRs)
+#define ATT_W8_MINW 8   // waves per SIMD the QB = 1, d <= 48 kernel is compiled for (8: 64 VGPRs, 6: 80 VGPRs)
 #endif
-template <int DQK, int DV, bool PRE, bool ONES>
-__global__ __launch_bounds__(512, (DV <= 3 ? ATT_W8_MINW : DQK <= 96 ? 2 : 1)) void k_attention_w8(AttnArgs a) {
+// second launch bound = waves per SIMD; QB = 2, DV 4: keep two workgroups per CU
+template <int DQK, int DV, bool PRE, bool ONES, int QB>
+__global__ __launch_bounds__(512, QB == 1 ? (DV <= 3 ? ATT_W8_MINW : DQK <= 96 ? 2 : 1) : (DV <= 3 ? 2 : 4))
+void k_attention_w8(AttnArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    static_assert(QB == 1 || QB == 2, "one or two query blocks per wave");
     constexpr int KS = DQK / 32;
     constexpr int NT = 512;
     constexpr int KCH = DQK / 8;
@@ -320,7 +335,7 @@ __global__ __launch_bounds__(512, (DV <= 3 ? ATT_W8_MINW : DQK <= 96 ? 2 : 1)) v
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, g = lane >> 4;
-    const int nqb = (a.Nq + 127) >> 7;
+    const int nqb = (a.Nq + QB * 128 - 1) >> (6 + QB);
     const int nwg = gridDim.x;
     int id = blockIdx.x;
     {
@@ -328,8 +343,8 @@ __global__ __launch_bounds__(512, (DV <= 3 ? ATT_W8_MINW : DQK <= 96 ? 2 : 1)) v
         id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
     }
     const int qb = id % nqb, h = (id / nqb) % a.heads, b = id / (nqb * a.heads);
-    const int qblk0 = qb * 128;
-    const int q0 = qblk0 + wave * 16;
+    const int qblk0 = qb * (QB * 128);
+    const int q0 = qblk0 + wave * (QB * 16);   // this wave's queries: QB fragments of 16
     const int d = a.d;
     const half_t* __restrict__ Qb = a.Q + (size_t)b * a.sQ + h * d;
     const half_t* Kb = a.K + (size_t)b * a.sK + h * d;
@@ -341,324 +356,28 @@ __global__ __launch_bounds__(512, (DV <= 3 ? ATT_W8_MINW : DQK <= 96 ? 2 : 1)) v
     const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(
         (void*)Vb, 0, (unsigned)(((size_t)(d - 1) * a.ldvt + nk8) * 2), 0x00020000);
 
-    half8 qf[KS];
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks) {
-        const int q = q0 + fr, d0 = (ks * 4 + g) * 8;
-        u32x4 v = {0u, 0u, 0u, 0u};
-        if (q < a.Nq && d0 < d) v = *reinterpret_cast<const u32x4*>(Qb + (size_t)q * a.ldq + d0);
-        qf[ks] = __builtin_bit_cast(half8, v);
-    }
-
-    floatx4 o[DV];
-#pragma unroll
-    for (int dt = 0; dt < DV; ++dt) o[dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float m_used = 0.f;  // running (lazy) max, in base-2 logit units
-    floatx4 init = {0.f, 0.f, 0.f, 0.f};  // PRE: -m_used, the QK^T accumulator input
-    float lrow = 0.f;
-
-    int ntiles = (a.Nk + 63) >> 6;
-    if (a.causal) {
-        const int qend = min(a.Nq, qblk0 + 128);
-        ntiles = min(ntiles, (qend + 63) >> 6);
-    }
-
-    // per-thread constant load offsets / LDS store addresses
-    unsigned kvo[KLD], vvo[VLD];
-    // LDS store offsets of this thread's K chunk (low 16 bits) and V^T chunk (high 16 bits) in ONE
-    // register: at the 64-VGPR budget of 8 waves/SIMD the separate V offset was spilled to scratch
-    // and reloaded (scratch_load + vmcnt(0)) in every K/V tile iteration
-    unsigned kvst[KLD > VLD ? KLD : VLD];
-    static_assert(2 * (KBYTES + VBYTES) < 65536 + 65536, "LDS offsets must fit 16 bits");
-    bool vones[VLD], vlive[VLD];
-#pragma unroll
-    for (int i = 0; i < KLD; ++i) {
-        const int e = tid + NT * i;
-        const int row = e / KCH, c = e - row * KCH;
-        kvo[i] = (e < 64 * KCH && c * 8 < d) ? (unsigned)(row * a.ldk + c * 8) * 2u : OOB;
-        kvst[i] = (unsigned)(row * KSTR + c * 16);
-    }
-#pragma unroll
-    for (int i = KLD; i < VLD; ++i) kvst[i] = 0u;
-#pragma unroll
-    for (int i = 0; i < VLD; ++i) {
-        const int e = tid + NT * i;
-        const int row = e >> 3, c = e & 7;
-        vvo[i] = (e < VROWS * 8 && row < d) ? (unsigned)(row * a.ldvt + c * 8) * 2u : OOB;
-        vones[i] = ONES && row == d;
-        vlive[i] = e < VROWS * 8 && row < d;
-        const int grp = c >> 2, cc = c & 3;
-        const int pos = grp * 32 + (cc & 1) * 16 + (cc >> 1) * 4;  // halfs (see k_attention)
-        kvst[i] |= (unsigned)(KBYTES + row * VSTR + pos * 2) << 16;
-        asm volatile("" : "+v"(kvst[i]));   // opaque: keeps the optimizer from un-packing the two halves again
-    }
-
-    u32x4 rk[KLD], rv[VLD];
-#define ATT_LOAD(J)                                                                           \
-    {                                                                                         \
-        const int key0 = (J) * 64;                                                            \
-        if (key0 + 64 <= a.Nk) { /* full tile: constant per-lane offsets + scalar tile offset */ \
-            _Pragma("unroll") for (int i = 0; i < KLD; ++i)                                   \
-                rk[i] = __builtin_amdgcn_raw_buffer_load_b128(rsK, kvo[i], key0 * a.ldk * 2, 0); \
-            _Pragma("unroll") for (int i = 0; i < VLD; ++i)                                   \
-                rv[i] = __builtin_amdgcn_raw_buffer_load_b128(rsV, vvo[i], key0 * 2, 0);      \
-        } else { /* ragged last tile: rows / key chunks past the end read zero */             \
-            _Pragma("unroll") for (int i = 0; i < KLD; ++i) {                                 \
-                const unsigned vo = (key0 + (tid + NT * i) / KCH < a.Nk) ? kvo[i] + (unsigned)key0 * a.ldk * 2u : OOB; /* row recomputed: rare path */ \
-                rk[i] = __builtin_amdgcn_raw_buffer_load_b128(rsK, vo, 0, 0);                 \
-            }                                                                                 \
-            _Pragma("unroll") for (int i = 0; i < VLD; ++i) {                                 \
-                const unsigned vo = (key0 + ((tid + NT * i) & 7) * 8 < nk8) ? vvo[i] + (unsigned)key0 * 2u : OOB; \
-                rv[i] = __builtin_amdgcn_raw_buffer_load_b128(rsV, vo, 0, 0);                 \
-            }                                                                                 \
-        }                                                                                     \
-    }
-#define ATT_STORE(BUF)                                                                        \
-    {                                                                                         \
-        char* sb = sKV + (BUF) * (KBYTES + VBYTES);                                           \
-        _Pragma("unroll") for (int i = 0; i < KLD; ++i)                                       \
-            if (KLD * NT == 64 * KCH || tid + NT * i < 64 * KCH)                              \
-                *reinterpret_cast<u32x4*>(sb + (kvst[i] & 0xffffu)) = rk[i];                               \
-        _Pragma("unroll") for (int i = 0; i < VLD; ++i)                                       \
-            if (vlive[i]) {                                                                   \
-                *reinterpret_cast<u32x2*>(sb + (kvst[i] >> 16)) = u32x2{rv[i][0], rv[i][1]};  \
-                *reinterpret_cast<u32x2*>(sb + (kvst[i] >> 16) + 16) = u32x2{rv[i][2], rv[i][3]}; \
-            }                                                                                 \
-    }
-
-    // V^T rows >= head_dim never change: zero padding, and with ONES row `d` = 1.0 so that the
-    // PV MFMA also accumulates the softmax denominator.  Written once, to both stages.
-#pragma unroll
-    for (int i = 0; i < VLD; ++i) {
-        const int e = tid + NT * i;
-        if (e < VROWS * 8 && !vlive[i]) {
-            const unsigned w = vones[i] ? 0x3C003C00u : 0u;
-#pragma unroll
-            for (int buf = 0; buf < 2; ++buf) {
-                char* sb = sKV + buf * (KBYTES + VBYTES);
-                *reinterpret_cast<u32x2*>(sb + (kvst[i] >> 16)) = u32x2{w, w};
-                *reinterpret_cast<u32x2*>(sb + (kvst[i] >> 16) + 16) = u32x2{w, w};
-            }
-        }
-    }
-    ATT_LOAD(0);
-    ATT_STORE(0);
-    __syncthreads();
-    const float c2 = a.scale_log2;
-    const floatx2 c2v = {c2, c2};
-
-    for (int j = 0; j < ntiles; ++j) {
-        if (j + 1 < ntiles) ATT_LOAD(j + 1);
-        const char* sK = sKV + (j & 1) * (KBYTES + VBYTES);
-        const char* sV = sK + KBYTES;
-        const bool need_mask = (j * 64 + 64 > a.Nk) || a.causal;
-        floatx4 s[4];
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks) {
-                const half8 kf = *reinterpret_cast<const half8*>(sK + (f * 16 + fr) * KSTR +
-                                                                 (ks * 4 + g) * 16);
-                s[f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[ks], ks == 0 ? init : s[f], 0, 0, 0);
-            }
-#if ATT_VPRE
-        // issue the V^T fragment reads before the softmax so their latency hides under it
-        constexpr int VP = DV <= 5 ? DV : 0;
-        half8 vfp[2][VP > 0 ? VP : 1];
-        if (VP > 0) {
-#pragma unroll
-            for (int kg = 0; kg < 2; ++kg)
-#pragma unroll
-                for (int dt = 0; dt < VP; ++dt)
-                    vfp[kg][dt] = *reinterpret_cast<const half8*>(sV + (dt * 16 + fr) * VSTR +
-                                                                  (kg * 4 + g) * 16);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#endif
-        if (!PRE) {
-            const floatx2 mv = {m_used, m_used};
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) {
-                    floatx2 x = {s[f][r], s[f][r + 1]};
-                    x = x * c2v - mv;
-                    s[f][r] = x[0];
-                    s[f][r + 1] = x[1];
-                }
-        }
-        if (need_mask) {
-            const int q = q0 + fr;
-            int kb = j * 64 + g * 4;   // opaque inside the branch: see k_attention
-            asm volatile("" : "+v"(kb));
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int key = kb + f * 16 + r;
-                    if (key >= a.Nk || (a.causal && key > q)) s[f][r] = -INFINITY;
-                }
-        }
-        // s = base-2 logits relative to the lazy max.  Lane-local max as 8 v_max3_f32: fmaxf()
-        // makes the compiler canonicalise every MFMA result first (16 extra v_max per tile)
-        float tmax;
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(s[0][0]), "v"(s[0][1]), "v"(s[0][2]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[0][3]), "v"(s[1][0]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[1][1]), "v"(s[1][2]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[1][3]), "v"(s[2][0]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[2][1]), "v"(s[2][2]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[2][3]), "v"(s[3][0]));
-        asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[3][1]), "v"(s[3][2]));
-        asm("v_max_f32 %0, %1, %2" : "=v"(tmax) : "v"(tmax), "v"(s[3][3]));
-        if (j == 0 || __any(tmax > LAZY_THR)) {
-            // advance the running max to the exact row max (rare after the first tiles)
-            const float t = xor_max_16_32(tmax);
-            float delta = (j == 0) ? t : fmaxf(t, 0.f);
-            if (delta == -INFINITY) delta = 0.f;
-            const float alpha = (j == 0) ? 1.f : __builtin_amdgcn_exp2f(-delta);
-            m_used += delta;
-            if (PRE) init = floatx4{-m_used, -m_used, -m_used, -m_used};
-            lrow *= alpha;
-#pragma unroll
-            for (int dt = 0; dt < DV; ++dt)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) o[dt][r] *= alpha;
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) s[f][r] -= delta;
-        }
-        half8 p[2];
-        floatx2 ps = {0.f, 0.f};
-#pragma unroll
-        for (int f = 0; f < 4; ++f)
-#pragma unroll
-            for (int r = 0; r < 4; r += 2) {
-                const floatx2 e = {__builtin_amdgcn_exp2f(s[f][r]), __builtin_amdgcn_exp2f(s[f][r + 1])};
-                if (!ONES) ps += e;
-                const half2v eh = __builtin_convertvector(e, half2v);
-                p[f >> 1][(f & 1) * 4 + r] = eh[0];
-                p[f >> 1][(f & 1) * 4 + r + 1] = eh[1];
-            }
-        if (!ONES) lrow += ps[0] + ps[1];
-#pragma unroll
-        for (int kg = 0; kg < 2; ++kg)
-#pragma unroll
-            for (int dt = 0; dt < DV; ++dt) {
-#if ATT_VPRE
-                const half8 vf = VP > 0 ? vfp[kg][VP > 0 ? dt : 0]
-                                        : *reinterpret_cast<const half8*>(sV + (dt * 16 + fr) * VSTR +
-                                                                          (kg * 4 + g) * 16);
-#else
-                const half8 vf = *reinterpret_cast<const half8*>(sV + (dt * 16 + fr) * VSTR +
-                                                                 (kg * 4 + g) * 16);
-#endif
-                o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, p[kg], o[dt], 0, 0, 0);
-            }
-        if (j + 1 < ntiles) ATT_STORE((j + 1) & 1);
-        __syncthreads();
-    }
-#undef ATT_LOAD
-#undef ATT_STORE
-
-    float l;
-    if (ONES) {
-        // denominator = O^T row d: lane group g = (d>>2)&3, fragment d>>4, element 0
-        float lv = 0.f;
-#pragma unroll
-        for (int dt = 0; dt < DV; ++dt)
-            if (dt == (d >> 4)) lv = o[dt][0];
-        l = __shfl(lv, ((d >> 2) & 3) * 16 + fr, 64);
-    } else {
-        l = lrow;
-        l += __shfl_xor(l, 16, 64);
-        l += __shfl_xor(l, 32, 64);
-    }
-    const float inv = 1.0f / l;
-    const int q = q0 + fr;
-    if (q < a.Nq) {
-#pragma unroll
-        for (int dt = 0; dt < DV; ++dt) {
-            const int d0 = dt * 16 + g * 4;
-            if (d0 >= d) continue;
-            half4 v;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) v[r] = (half_t)(o[dt][r] * inv);
-            *reinterpret_cast<half4*>(Ob + (size_t)q * a.ldo + d0) = v;
-        }
-    }
-#endif
-}
-
-// ---------------------------------------------------------------------------------------
-// Two 16-query blocks per wave (256 queries per workgroup).  On this chip the instructions of
-// a SIMD's waves ADD UP (tools/micro/pipe_overlap.hip: no overlap between v_mfma_f32_16x16x32
-// and VALU / DS issue), so the tile loop is bound by its instruction count per score.  Both
-// query blocks share every K and V^T fragment read and the K / V^T tile staging: DS
-// instructions and global loads per score halve; MFMA, exp and convert counts per score are
-// unchanged.  ~125 VGPRs (4 waves per SIMD: the kernel is not sensitive to occupancy,
-// tools/ab_attn_occ.py).  Same arithmetic per query as k_attention_w8.
-template <int DQK, int DV, bool PRE, bool ONES>
-__global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnArgs a) {   // (second bound = waves per SIMD; DV 4: keep two workgroups per CU)
-#if defined(__HIP_DEVICE_COMPILE__)
-    constexpr int KS = DQK / 32;
-    constexpr int NT = 512;
-    constexpr int KCH = DQK / 8;
-    constexpr int KSTR = (KCH + 2) * 16;
-    constexpr int VSTR = 10 * 16;
-    constexpr int VROWS = DV * 16;
-    constexpr int KLD = (64 * KCH + NT - 1) / NT;
-    constexpr int VLD = (VROWS * 8 + NT - 1) / NT;
-    constexpr int KBYTES = 64 * KSTR, VBYTES = VROWS * VSTR;
-    constexpr unsigned OOB = 0x7fffffffu;
-    __shared__ __attribute__((aligned(16))) char sKV[2 * (KBYTES + VBYTES)];
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int fr = lane & 15, g = lane >> 4;
-    const int nqb = (a.Nq + 255) >> 8;
-    const int nwg = gridDim.x;
-    int id = blockIdx.x;
-    {
-        const int q = nwg >> 3, r = nwg & 7, xcd = id & 7, slot = id >> 3;
-        id = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + slot;
-    }
-    const int qb = id % nqb, h = (id / nqb) % a.heads, b = id / (nqb * a.heads);
-    const int qblk0 = qb * 256;
-    const int q0 = qblk0 + wave * 32;   // this wave's queries: q0 .. q0+31 (two fragments of 16)
-    const int d = a.d;
-    const half_t* __restrict__ Qb = a.Q + (size_t)b * a.sQ + h * d;
-    const half_t* Kb = a.K + (size_t)b * a.sK + h * d;
-    const half_t* Vb = a.Vt + (size_t)b * a.sVt + (size_t)h * d * a.ldvt;
-    half_t* __restrict__ Ob = a.O + (size_t)b * a.sO + h * d;
-    const int nk8 = (a.Nk + 7) & ~7;
-    const __amdgpu_buffer_rsrc_t rsK = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)Kb, 0, (unsigned)(((size_t)(a.Nk - 1) * a.ldk + d) * 2), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsV = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)Vb, 0, (unsigned)(((size_t)(d - 1) * a.ldvt + nk8) * 2), 0x00020000);
-
-    half8 qf[2][KS];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
+    half8 qf[QB][KS];
+    ATT_EACH_BLOCK(
+        _Pragma("unroll") for (int ks = 0; ks < KS; ++ks) {
             const int q = q0 + t * 16 + fr, d0 = (ks * 4 + g) * 8;
             u32x4 v = {0u, 0u, 0u, 0u};
             if (q < a.Nq && d0 < d) v = *reinterpret_cast<const u32x4*>(Qb + (size_t)q * a.ldq + d0);
             qf[t][ks] = __builtin_bit_cast(half8, v);
-        }
+        })
 
-    floatx4 o[2][DV];
-#pragma unroll
-    for (int t = 0; t < 2; ++t)
-#pragma unroll
-        for (int dt = 0; dt < DV; ++dt) o[t][dt] = floatx4{0.f, 0.f, 0.f, 0.f};
-    float m_used[2] = {0.f, 0.f};  // running (lazy) max per query block, in base-2 logit units
-    floatx4 init[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};  // PRE: -m_used, the QK^T accumulator input
-    float lrow[2] = {0.f, 0.f};
+    floatx4 o[QB][DV];
+    float m_used[QB];  // running (lazy) max per query block, in base-2 logit units
+    floatx4 init[QB];  // PRE: -m_used, the QK^T accumulator input
+    float lrow[QB];
+    ATT_EACH_BLOCK(
+        _Pragma("unroll") for (int dt = 0; dt < DV; ++dt) o[t][dt] = floatx4{0.f, 0.f, 0.f, 0.f};
+        m_used[t] = 0.f;
+        init[t] = floatx4{0.f, 0.f, 0.f, 0.f};
+        lrow[t] = 0.f;)
 
     int ntiles = (a.Nk + 63) >> 6;
     if (a.causal) {
-        const int qend = min(a.Nq, qblk0 + 256);
+        const int qend = min(a.Nq, qblk0 + QB * 128);
         ntiles = min(ntiles, (qend + 63) >> 6);
     }
 
@@ -751,31 +470,22 @@ __global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnA
         const char* sK = sKV + (j & 1) * (KBYTES + VBYTES);
         const char* sV = sK + KBYTES;
         const bool need_mask = (j * 64 + 64 > a.Nk) || a.causal;
-        floatx4 s[2][4];
-#if ATT_SETPRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
+        floatx4 s[QB][4];
+        const floatx4 zacc = {0.f, 0.f, 0.f, 0.f};   // !PRE: the max is subtracted after the MFMA, init[] stays unused
 #pragma unroll
         for (int f = 0; f < 4; ++f)
 #pragma unroll
             for (int ks = 0; ks < KS; ++ks) {
                 const half8 kf = *reinterpret_cast<const half8*>(sK + (f * 16 + fr) * KSTR +
                                                                  (ks * 4 + g) * 16);
-                s[0][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[0][ks], ks == 0 ? init[0] : s[0][f], 0, 0, 0);
-                s[1][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[1][ks], ks == 0 ? init[1] : s[1][f], 0, 0, 0);
+                ATT_EACH_BLOCK(s[t][f] = __builtin_amdgcn_mfma_f32_16x16x32_f16(kf, qf[t][ks], ks != 0 ? s[t][f] : PRE ? init[t] : zacc, 0, 0, 0);)
             }
-#if ATT_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-        half8 p[2][2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
+        half8 p[QB][2];
+        ATT_EACH_BLOCK(
             if (!PRE) {
                 const floatx2 mv = {m_used[t], m_used[t]};
-#pragma unroll
-                for (int f = 0; f < 4; ++f)
-#pragma unroll
-                    for (int r = 0; r < 4; r += 2) {
+                _Pragma("unroll") for (int f = 0; f < 4; ++f)
+                    _Pragma("unroll") for (int r = 0; r < 4; r += 2) {
                         floatx2 x = {s[t][f][r], s[t][f][r + 1]};
                         x = x * c2v - mv;
                         s[t][f][r] = x[0];
@@ -786,14 +496,14 @@ __global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnA
                 const int q = q0 + t * 16 + fr;
                 int kb = j * 64 + g * 4;   // opaque inside the branch: see k_attention
                 asm volatile("" : "+v"(kb));
-#pragma unroll
-                for (int f = 0; f < 4; ++f)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
+                _Pragma("unroll") for (int f = 0; f < 4; ++f)
+                    _Pragma("unroll") for (int r = 0; r < 4; ++r) {
                         const int key = kb + f * 16 + r;
                         if (key >= a.Nk || (a.causal && key > q)) s[t][f][r] = -INFINITY;
                     }
             }
+            // s = base-2 logits relative to the lazy max.  Lane-local max as 8 v_max3_f32: fmaxf()
+            // makes the compiler canonicalise every MFMA result first (16 extra v_max per tile)
             float tmax;
             asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(s[t][0][0]), "v"(s[t][0][1]), "v"(s[t][0][2]));
             asm("v_max3_f32 %0, %1, %2, %3" : "=v"(tmax) : "v"(tmax), "v"(s[t][0][3]), "v"(s[t][1][0]));
@@ -812,57 +522,41 @@ __global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnA
                 m_used[t] += delta;
                 if (PRE) init[t] = floatx4{-m_used[t], -m_used[t], -m_used[t], -m_used[t]};
                 lrow[t] *= alpha;
-#pragma unroll
-                for (int dt = 0; dt < DV; ++dt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) o[t][dt][r] *= alpha;
-#pragma unroll
-                for (int f = 0; f < 4; ++f)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s[t][f][r] -= delta;
+                _Pragma("unroll") for (int dt = 0; dt < DV; ++dt)
+                    _Pragma("unroll") for (int r = 0; r < 4; ++r) o[t][dt][r] *= alpha;
+                _Pragma("unroll") for (int f = 0; f < 4; ++f)
+                    _Pragma("unroll") for (int r = 0; r < 4; ++r) s[t][f][r] -= delta;
             }
             floatx2 ps = {0.f, 0.f};
-#pragma unroll
-            for (int f = 0; f < 4; ++f)
-#pragma unroll
-                for (int r = 0; r < 4; r += 2) {
+            _Pragma("unroll") for (int f = 0; f < 4; ++f)
+                _Pragma("unroll") for (int r = 0; r < 4; r += 2) {
                     const floatx2 e = {__builtin_amdgcn_exp2f(s[t][f][r]), __builtin_amdgcn_exp2f(s[t][f][r + 1])};
                     if (!ONES) ps += e;
                     const half2v eh = __builtin_convertvector(e, half2v);
                     p[t][f >> 1][(f & 1) * 4 + r] = eh[0];
                     p[t][f >> 1][(f & 1) * 4 + r + 1] = eh[1];
                 }
-            if (!ONES) lrow[t] += ps[0] + ps[1];
-        }
-#if ATT_SETPRIO
-        __builtin_amdgcn_s_setprio(1);
-#endif
+            if (!ONES) lrow[t] += ps[0] + ps[1];)
 #pragma unroll
         for (int kg = 0; kg < 2; ++kg)
 #pragma unroll
             for (int dt = 0; dt < DV; ++dt) {
                 const half8 vf = *reinterpret_cast<const half8*>(sV + (dt * 16 + fr) * VSTR +
                                                                  (kg * 4 + g) * 16);
-                o[0][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, p[0][kg], o[0][dt], 0, 0, 0);
-                o[1][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, p[1][kg], o[1][dt], 0, 0, 0);
+                ATT_EACH_BLOCK(o[t][dt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(vf, p[t][kg], o[t][dt], 0, 0, 0);)
             }
-#if ATT_SETPRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
         if (j + 1 < ntiles) ATT_STORE((j + 1) & 1);
         __syncthreads();
     }
 #undef ATT_LOAD
 #undef ATT_STORE
 
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
+    ATT_EACH_BLOCK(
         float l;
         if (ONES) {
             // denominator = O^T row d: lane group g = (d>>2)&3, fragment d>>4, element 0
             float lv = 0.f;
-#pragma unroll
-            for (int dt = 0; dt < DV; ++dt)
+            _Pragma("unroll") for (int dt = 0; dt < DV; ++dt)
                 if (dt == (d >> 4)) lv = o[t][dt][0];
             l = __shfl(lv, ((d >> 2) & 3) * 16 + fr, 64);
         } else {
@@ -873,22 +567,20 @@ __global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnA
         const float inv = 1.0f / l;
         const int q = q0 + t * 16 + fr;
         if (q < a.Nq) {
-#pragma unroll
-            for (int dt = 0; dt < DV; ++dt) {
+            _Pragma("unroll") for (int dt = 0; dt < DV; ++dt) {
                 const int d0 = dt * 16 + g * 4;
                 if (d0 >= d) continue;
                 half4 v;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) v[r] = (half_t)(o[t][dt][r] * inv);
+                _Pragma("unroll") for (int r = 0; r < 4; ++r) v[r] = (half_t)(o[t][dt][r] * inv);
                 *reinterpret_cast<half4*>(Ob + (size_t)q * a.ldo + d0) = v;
             }
-        }
-    }
+        })
+#undef ATT_EACH_BLOCK
 #endif
 }
 
 // ---------------------------------------------------------------------------------------
-// head_dim 40, Q pre-scaled: k_attention_w8q2 with the QK^T product on v_mfma_f32_32x32x16_f16.
+// head_dim 40, Q pre-scaled: the two-block k_attention_w8 with the QK^T product on v_mfma_f32_32x32x16_f16.
 // The 16x16x32 form contracts 32 head-dim columns per instruction, so head_dim 40 costs 64
 // columns (37.5 % zeros); the 32x32x16 form contracts 16, so 40 costs 48 -- 6 MFMAs of 32
 // passes per 64-key tile and 32 queries instead of 16 of 16 passes (-25 % matrix-pipe time on
@@ -904,7 +596,7 @@ __global__ __launch_bounds__(512, (DV <= 3 ? 2 : 4)) void k_attention_w8q2(AttnA
 //    v_permlane16_swap (8 per tile), which turns the 32x32 accumulator layout into two 16-query B
 //    operands; the key order inside each 32-key group that this produces is baked into the LDS
 //    image of V^T (k slot (g, e) <-> key 8 ((g & 1) + 2 (e >> 2)) + 4 (g >> 1) + (e & 3)).
-// Same lazy max, same fused denominator (ones row of V^T), same staging as k_attention_w8q2.
+// Same lazy max, same fused denominator (ones row of V^T), same staging as k_attention_w8.
 __global__ __launch_bounds__(512, 4) void k_attention_w8q2m(AttnArgs a) {   // (HIP: the second bound is waves per SIMD: <= 128 VGPRs, two workgroups per CU)
 #if defined(__HIP_DEVICE_COMPILE__)
     constexpr int NT = 512;
@@ -1151,11 +843,92 @@ __global__ __launch_bounds__(512, 4) void k_attention_w8q2m(AttnArgs a) {   // (
 #endif
 }
 
-extern "C" int fd_attention_f16(const fd_attention_desc* d, void* stream) {
-    if (fd_plan_recording() && d) {
-        const fd_attention_desc dc_ = *d;
-        fd_plan_push([dc_](void* fd_s_) -> int { return fd_attention_f16(&dc_, fd_s_); });
+// ---------------------------------------------------------------------------------------
+// Host side: check the descriptor, choose the kernel, launch it.
+typedef void (*attn_kernel_t)(AttnArgs);
+
+// The four A/B switches, read once per process.
+struct AttnSwitches {
+    int wide;   // FD_ATTN_QT1: 0 = 4-wave / 32-query kernel, 1 = 8-wave kernel with the exact running max,
+                // 2 (default) = 8-wave kernel with the VALU-lean softmax (lazy max, fused denominator)
+    int q2;     // FD_ATTN_Q2=0: one query block per wave on the long self-attention rows too
+    int q2_64;  // FD_ATTN_Q2_64=0: one query block per wave at head dims 49..64
+    int m32;    // FD_ATTN_M32=0: the 16x16x32 QK^T form for head_dim 40 too
+};
+static const AttnSwitches& attn_switches() {
+    static const AttnSwitches sw = {
+        getenv("FD_ATTN_QT1") ? atoi(getenv("FD_ATTN_QT1")) : 2,
+        getenv("FD_ATTN_Q2") ? atoi(getenv("FD_ATTN_Q2")) : 1,
+        getenv("FD_ATTN_Q2_64") ? atoi(getenv("FD_ATTN_Q2_64")) : 1,
+        getenv("FD_ATTN_M32") ? atoi(getenv("FD_ATTN_M32")) : 1,
+    };
+    return sw;
+}
+
+// Head-dim bands: the exact-max kernels of each (4 waves; 8 waves where FD_ATTN_QT1=1 has one) and whether the band has
+// lazy-max kernels at all (81..128 does not: k_attention whatever the switch says, and q_prescaled is refused).
+struct AttnBand {
+    int max_hd, dqk, dv;
+    bool lazy;
+    attn_kernel_t w4, w8;
+};
+static const AttnBand ATTN_BANDS[] = {
+    {48, 64, 3, true, k_attention<64, 3>, k_attention<64, 3, 1, 8>},
+    {64, 64, 4, true, k_attention<64, 4>, k_attention<64, 4, 1, 8>},
+    {80, 96, 5, true, k_attention<96, 5>, k_attention<96, 5, 1, 8>},
+    {96, 96, 6, false, k_attention<96, 6>, nullptr},
+    {128, 128, 8, false, k_attention<128, 8>, nullptr},
+    {160, 160, 10, true, k_attention<160, 10>, k_attention<160, 10, 1, 8>},
+};
+// The lazy-max instantiations, both PRE twins of each (DQK, DV, ONES, QB).
+struct AttnLazyRow {
+    int dqk, dv;
+    bool ones;
+    int qb;
+    attn_kernel_t plain, pre;
+};
+static const AttnLazyRow ATTN_LAZY[] = {
+    {64, 3, true, 1, k_attention_w8<64, 3, false, true, 1>, k_attention_w8<64, 3, true, true, 1>},
+    {64, 3, false, 1, k_attention_w8<64, 3, false, false, 1>, k_attention_w8<64, 3, true, false, 1>},
+    {64, 4, false, 1, k_attention_w8<64, 4, false, false, 1>, k_attention_w8<64, 4, true, false, 1>},
+    {96, 5, false, 1, k_attention_w8<96, 5, false, false, 1>, k_attention_w8<96, 5, true, false, 1>},
+    {160, 10, false, 1, k_attention_w8<160, 10, false, false, 1>, k_attention_w8<160, 10, true, false, 1>},
+    {64, 3, true, 2, k_attention_w8<64, 3, false, true, 2>, k_attention_w8<64, 3, true, true, 2>},
+    {64, 3, false, 2, k_attention_w8<64, 3, false, false, 2>, k_attention_w8<64, 3, true, false, 2>},
+    {64, 4, false, 2, k_attention_w8<64, 4, false, false, 2>, k_attention_w8<64, 4, true, false, 2>},
+};
+
+struct AttnChoice {
+    attn_kernel_t kernel;
+    int rows;      // queries per workgroup: 128 or 256
+    int threads;   // 256 or 512
+};
+// The kernel for a checked descriptor (head_dim a multiple of 8 in 8..160; pre only where attn_check lets it through).
+static AttnChoice attn_choose(int hd, int n_q, int n_k, bool pre, const AttnSwitches& sw) {
+    const AttnBand* band = ATTN_BANDS;
+    while (hd > band->max_hd) ++band;
+    if (sw.wide != 2 || !band->lazy) {
+        const bool w8 = sw.wide && band->w8;
+        return {w8 ? band->w8 : band->w4, 128, w8 ? 512 : 256};
     }
+    // two query blocks per wave for the long self-attention rows (FD_ATTN_Q2=0: one block, A/B)
+    int qb = 1;
+    if (sw.q2 && n_q >= 2048) {
+        // also on the short text-context rows (n_k = 77): K / V^T staging per query halves (38.6 -> 36.9 us at 16x4096 queries)
+        const int q2_mink = 64;
+        if (hd <= 48 && n_k >= q2_mink) qb = 2;
+        // head dims 49..64 (SD2.1: 64): the same two-block kernel with four O^T fragments (FD_ATTN_Q2_64=0: one block per wave, A/B)
+        if (hd > 48 && hd <= 64 && sw.q2_64 && n_k >= 1024) qb = 2;
+    }
+    // FD_ATTN_M32=0: the 16x16x32 QK^T form for head_dim 40 too (A/B)
+    if (qb == 2 && hd == 40 && pre && sw.m32) return {k_attention_w8q2m, 256, 512};
+    const bool ones = hd <= 40;   // a padding row of V^T right behind the head carries the softmax denominator
+    for (const AttnLazyRow& r : ATTN_LAZY)
+        if (r.dqk == band->dqk && r.dv == band->dv && r.ones == ones && r.qb == qb) return {pre ? r.pre : r.plain, 128 * qb, 512};
+    return {nullptr, 0, 0};
+}
+
+static int attn_check(const fd_attention_desc* d, const AttnSwitches& sw, AttnArgs& a) {
     FD_CHECK_ARG(d && d->Q && d->K && d->Vt && d->O, FD_EINVAL, "fd_attention_f16: null pointer");
     FD_CHECK_ARG(d->batch > 0 && d->heads > 0 && d->n_q > 0 && d->n_k > 0, FD_EINVAL,
                  "fd_attention_f16: non-positive dimension");
@@ -1165,7 +938,9 @@ extern "C" int fd_attention_f16(const fd_attention_desc* d, void* stream) {
                  FD_ESHAPE, "fd_attention_f16: leading dimensions must be multiples of 8");
     FD_CHECK_ARG(d->ldvt >= ((d->n_k + 7) & ~7), FD_ESHAPE,
                  "fd_attention_f16: ldvt=%d < n_k rounded up to 8", d->ldvt);
-    AttnArgs a;
+    const int hd = d->head_dim;
+    FD_CHECK_ARG(!d->q_prescaled || (sw.wide == 2 && (hd <= 80 || hd > 128)), FD_ESHAPE,
+                 "fd_attention_f16: q_prescaled is not supported for head_dim=%d", hd);
     a.Q = (const half_t*)d->Q; a.K = (const half_t*)d->K; a.Vt = (const half_t*)d->Vt;
     a.O = (half_t*)d->O;
     a.sQ = d->q_sample_stride; a.sK = d->k_sample_stride; a.sVt = d->vt_sample_stride;
@@ -1176,69 +951,26 @@ extern "C" int fd_attention_f16(const fd_attention_desc* d, void* stream) {
     const float scale = d->scale > 0.f ? d->scale : 1.0f / sqrtf((float)d->head_dim);
     a.scale_log2 = scale * 1.4426950408889634f;
     if (d->q_prescaled) a.scale_log2 = 1.0f;
+    return FD_OK;
+}
+
+extern "C" int fd_attention_f16(const fd_attention_desc* d, void* stream) {
+    if (fd_plan_recording() && d) {
+        const fd_attention_desc dc_ = *d;
+        fd_plan_push([dc_](void* fd_s_) -> int { return fd_attention_f16(&dc_, fd_s_); });
+    }
+    const AttnSwitches& sw = attn_switches();
+    AttnArgs a;
+    const int rc = attn_check(d, sw, a);
+    if (rc != FD_OK) return rc;
+    const AttnChoice c = attn_choose(d->head_dim, d->n_q, d->n_k, d->q_prescaled != 0, sw);
+    FD_CHECK_ARG(c.kernel, FD_ESHAPE, "fd_attention_f16: no kernel for head_dim=%d", d->head_dim);   // a hole in ATTN_LAZY
     hipStream_t st = (hipStream_t)stream;
-    dim3 grid(fd_cdiv(d->n_q, 128) * d->heads * d->batch);
+    dim3 grid(fd_cdiv(d->n_q, c.rows) * d->heads * d->batch);
     const double flops = 4.0 * (double)d->batch * d->heads * (double)d->n_q * d->n_k * d->head_dim *
                          (d->causal ? 0.5 : 1.0);
     fd_prof_begin(FD_FAMILY_ATTENTION, st, flops, -1.0, fd_tag(6u, d->batch * d->heads, d->n_q, d->n_k, d->head_dim));
-    const int hd = d->head_dim;
-    // FD_ATTN_QT1: 0 = 4-wave / 32-query kernel, 1 = 8-wave kernel with the exact running max,
-    // 2 (default) = 8-wave kernel with the VALU-lean softmax (lazy max, fused denominator)
-    static const int wide = getenv("FD_ATTN_QT1") ? atoi(getenv("FD_ATTN_QT1")) : 2;
-    const bool pre = d->q_prescaled != 0;
-    // two query blocks per wave for the long self-attention rows (FD_ATTN_Q2=0: one block, A/B)
-    static const int q2 = getenv("FD_ATTN_Q2") ? atoi(getenv("FD_ATTN_Q2")) : 1;
-    FD_CHECK_ARG(!pre || (wide == 2 && (hd <= 80 || hd > 128)), FD_ESHAPE,
-                 "fd_attention_f16: q_prescaled is not supported for head_dim=%d", hd);
-#define ATT_W8(DQK, DV, ONES)                                                                  \
-    {                                                                                          \
-        if (pre) hipLaunchKernelGGL((k_attention_w8<DQK, DV, true, ONES>), grid, dim3(512), 0, st, a); \
-        else hipLaunchKernelGGL((k_attention_w8<DQK, DV, false, ONES>), grid, dim3(512), 0, st, a);    \
-    }
-    // also on the short text-context rows (n_k = 77): K / V^T staging per query halves (38.6 -> 36.9 us at 16x4096 queries)
-    const int q2_mink = 64;
-    // head dims 49..64 (SD2.1: 64): the same two-block kernel with four O^T fragments (FD_ATTN_Q2_64=0: one block per wave, A/B)
-    static const int q2_64 = getenv("FD_ATTN_Q2_64") ? atoi(getenv("FD_ATTN_Q2_64")) : 1;
-    if (hd > 48 && hd <= 64 && wide == 2 && q2 && q2_64 && d->n_q >= 2048 && d->n_k >= 1024) {
-        dim3 grid2(fd_cdiv(d->n_q, 256) * d->heads * d->batch);
-        if (pre) hipLaunchKernelGGL((k_attention_w8q2<64, 4, true, false>), grid2, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_attention_w8q2<64, 4, false, false>), grid2, dim3(512), 0, st, a);
-    } else if (hd <= 48 && wide == 2 && q2 && d->n_q >= 2048 && d->n_k >= q2_mink) {
-        dim3 grid2(fd_cdiv(d->n_q, 256) * d->heads * d->batch);
-        // FD_ATTN_M32=0: the 16x16x32 QK^T form for head_dim 40 too (A/B)
-        static const int m32 = getenv("FD_ATTN_M32") ? atoi(getenv("FD_ATTN_M32")) : 1;
-        if (hd == 40 && pre && m32) {
-            hipLaunchKernelGGL(k_attention_w8q2m, grid2, dim3(512), 0, st, a);
-        } else if (hd <= 40) {
-            if (pre) hipLaunchKernelGGL((k_attention_w8q2<64, 3, true, true>), grid2, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_attention_w8q2<64, 3, false, true>), grid2, dim3(512), 0, st, a);
-        } else {
-            if (pre) hipLaunchKernelGGL((k_attention_w8q2<64, 3, true, false>), grid2, dim3(512), 0, st, a);
-            else hipLaunchKernelGGL((k_attention_w8q2<64, 3, false, false>), grid2, dim3(512), 0, st, a);
-        }
-    } else if (hd <= 48) {
-        if (wide == 2 && hd <= 40) ATT_W8(64, 3, true)
-        else if (wide == 2) ATT_W8(64, 3, false)
-        else if (wide) hipLaunchKernelGGL((k_attention<64, 3, 1, 8>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_attention<64, 3>), grid, dim3(256), 0, st, a);
-    } else if (hd <= 64) {
-        if (wide == 2) ATT_W8(64, 4, false)
-        else if (wide) hipLaunchKernelGGL((k_attention<64, 4, 1, 8>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_attention<64, 4>), grid, dim3(256), 0, st, a);
-    } else if (hd <= 80) {
-        if (wide == 2) ATT_W8(96, 5, false)
-        else if (wide) hipLaunchKernelGGL((k_attention<96, 5, 1, 8>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_attention<96, 5>), grid, dim3(256), 0, st, a);
-    } else if (hd <= 96) {
-        hipLaunchKernelGGL((k_attention<96, 6>), grid, dim3(256), 0, st, a);
-    } else if (hd <= 128) {
-        hipLaunchKernelGGL((k_attention<128, 8>), grid, dim3(256), 0, st, a);
-    } else {
-        if (wide == 2) ATT_W8(160, 10, false)
-        else if (wide) hipLaunchKernelGGL((k_attention<160, 10, 1, 8>), grid, dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((k_attention<160, 10>), grid, dim3(256), 0, st, a);
-    }
-#undef ATT_W8
+    hipLaunchKernelGGL(c.kernel, grid, dim3(c.threads), 0, st, a);
     fd_prof_end(FD_FAMILY_ATTENTION, st);
     FD_CHECK_LAUNCH("k_attention");
     return FD_OK;

@@ -64,35 +64,35 @@ _TABLE = [
     _c(1, 2, 127, 63, 104, layout='out_slice'), _c(1, 2, 64, 200, 120, 'causal'), _c(1, 1, 1, 1, 112),
     # refused: q_prescaled has no kernel at head_dim 81..128
     _c(1, 2, 64, 64, 88, 'pre'), _c(1, 2, 64, 64, 128, 'pre'),
-    # ---- k_attention_w8<64, 3, *, true>: head_dim <= 40, denominator from the ones row right after the head ------------------
+    # ---- k_attention_w8<64, 3, *, true, 1>: head_dim <= 40, denominator from the ones row right after the head ---------------
     _c(2, 4, 129, 65, 8), _c(2, 2, 17, 8, 8, 'pre'), _c(2, 3, 127, 127, 16, 'pre', layout='merged_qk'), _c(1, 2, 64, 63, 16),
     _c(1, 5, 257, 77, 24, layout='padded_ld'), _c(2, 2, 1, 1, 24, 'pre'), _c(2, 2, 256, 320, 32, 'pre', layout='out_slice'),
     _c(1, 2, 2047, 64, 32), _c(2, 8, 256, 77, 40, 'pre'), _c(2, 8, 256, 256, 40, layout='merged_qk'),
     _c(1, 8, 1024, 1024, 40, 'pre', layout='merged_qk'), _c(1, 2, 2047, 1024, 40, 'pre'), _c(1, 2, 2048, 63, 40, 'pre'),
     _c(2, 2, 129, 65, 40, 'scale', layout='padded_ld'), _c(1, 2, 200, 77, 40, 'causal', 'pre'), _c(1, 2, 77, 200, 32, 'causal'),
-    # ---- k_attention_w8<64, 3, *, false>: head_dim 41..48 ---------------------------------------------------------------------
+    # ---- k_attention_w8<64, 3, *, false, 1>: head_dim 41..48 ------------------------------------------------------------------
     _c(2, 2, 130, 200, 48, 'pre'), _c(2, 2, 192, 192, 48, layout='merged_qk'), _c(1, 3, 2047, 65, 48, 'pre', layout='padded_ld'),
     _c(1, 1, 127, 1, 48, layout='out_slice'),
-    # ---- k_attention_w8<64, 4, *, false>: head_dim 49..64 ---------------------------------------------------------------------
+    # ---- k_attention_w8<64, 4, *, false, 1>: head_dim 49..64 ------------------------------------------------------------------
     _c(2, 12, 77, 77, 64, 'causal', layout='merged_qk'), _c(1, 16, 257, 257, 64), _c(2, 2, 129, 8, 56, 'pre', layout='padded_ld'),
     _c(1, 2, 2048, 1023, 64, 'pre'), _c(1, 2, 2047, 1024, 64), _c(2, 2, 100, 100, 64, 'pre', 'scale', layout='out_slice'),
     _c(1, 12, 77, 77, 64, 'causal', 'pre'),
-    # ---- k_attention_w8<96, 5, *, false>: head_dim 65..80 ---------------------------------------------------------------------
+    # ---- k_attention_w8<96, 5, *, false, 1>: head_dim 65..80 ------------------------------------------------------------------
     _c(1, 8, 1024, 1024, 80, 'pre', layout='merged_qk'), _c(1, 8, 2304, 2304, 80, 'pre', layout='merged_qk'),
     _c(1, 8, 1024, 1024, 80), _c(1, 16, 257, 257, 80), _c(2, 2, 129, 65, 72, layout='padded_ld'),
     _c(2, 3, 17, 63, 72, 'pre', layout='out_slice'), _c(1, 2, 250, 250, 80, 'causal', 'scale'),
-    # ---- k_attention_w8<160, 10, *, false>: head_dim 129..160 -----------------------------------------------------------------
+    # ---- k_attention_w8<160, 10, *, false, 1>: head_dim 129..160 --------------------------------------------------------------
     _c(2, 8, 256, 256, 160, 'pre', layout='merged_qk'), _c(1, 8, 576, 576, 160, 'pre', layout='merged_qk'),
     _c(2, 8, 144, 144, 160, layout='merged_qk'), _c(1, 8, 256, 256, 160), _c(1, 2, 100, 77, 160, 'pre', layout='padded_ld'),
     _c(2, 1, 129, 65, 136, 'scale', layout='out_slice'), _c(1, 3, 127, 1, 152), _c(1, 2, 64, 130, 160, 'causal', 'pre'),
-    # ---- k_attention_w8q2<64, 3, *, true>: n_q >= 2048, n_k >= 64, head_dim <= 40 (40 only when not prescaled) ------------------
+    # ---- k_attention_w8<64, 3, *, true, 2>: n_q >= 2048, n_k >= 64, head_dim <= 40 (40 only when not prescaled) ---------------
     _c(1, 2, 2048, 64, 32, 'pre'), _c(1, 1, 2048, 2048, 40, layout='merged_qk'), _c(2, 2, 2100, 200, 24, layout='padded_ld'),
     _c(2, 1, 2304, 136, 16, 'pre', layout='out_slice'), _c(1, 3, 2048, 64, 8, 'scale'), _c(1, 1, 2500, 2100, 32, 'causal', 'pre'),
     _c(1, 1, 2048, 2300, 40, 'causal'), _c(1, 2, 2048, 1024, 40),
-    # ---- k_attention_w8q2<64, 3, *, false>: head_dim 41..48 -------------------------------------------------------------------
+    # ---- k_attention_w8<64, 3, *, false, 2>: head_dim 41..48 ------------------------------------------------------------------
     _c(1, 2, 2200, 1100, 48), _c(2, 2, 2100, 64, 48, 'pre', layout='padded_ld'), _c(2, 1, 2048, 2048, 48, 'pre', layout='merged_qk'),
     _c(1, 1, 2049, 65, 48, 'scale', layout='out_slice'),
-    # ---- k_attention_w8q2<64, 4, *, false>: head_dim 49..64, n_k >= 1024 --------------------------------------------------------
+    # ---- k_attention_w8<64, 4, *, false, 2>: head_dim 49..64, n_k >= 1024 -----------------------------------------------------
     _c(2, 2, 2304, 2304, 64, 'pre', layout='merged_qk'), _c(2, 2, 2100, 1030, 56, layout='padded_ld'), _c(1, 1, 2048, 1024, 64),
     _c(1, 1, 2048, 2048, 64, 'causal', 'pre', layout='out_slice'), _c(1, 1, 2050, 1024, 56, 'pre', 'scale'),
     # ---- k_attention_w8q2m: head_dim 40, prescaled ----------------------------------------------------------------------------
@@ -111,9 +111,14 @@ def template_of(name: str) -> str:
     return name.split('<')[0]
 
 
+def family_of(name: str) -> tuple:
+    '''(template, QB): QB, the query blocks per wave, is the last argument of k_attention_w8 and None for the others.'''
+    t = template_of(name)
+    return t, int(name[:-1].split(', ')[-1]) if t == 'k_attention_w8' else None
+
+
 def expected_kernel(case: Case, env={}) -> str:
-    '''The instantiation fd_attention_f16 launches for `case`, spelled as in csrc/attention.hip (the ATT_W8 macro
-    expanded), under the FD_ATTN_* variables in `env`.  ValueError where the library answers FD_ESHAPE.'''
+    '''The instantiation fd_attention_f16 launches for `case`, spelled as in the tables of csrc/attention.hip, under the FD_ATTN_* variables in `env`.  ValueError where the library answers FD_ESHAPE.'''
     wide = int(env.get('FD_ATTN_QT1', 2))
     q2 = int(env.get('FD_ATTN_Q2', 1))
     q2_64 = int(env.get('FD_ATTN_Q2_64', 1))
@@ -129,22 +134,22 @@ def expected_kernel(case: Case, env={}) -> str:
         return f'k_attention<{dqk}, {dv}, 1, 8>' if wide else f'k_attention<{dqk}, {dv}>'
 
     if 48 < hd <= 64 and wide == 2 and q2 and q2_64 and case.n_q >= 2048 and case.n_k >= 1024:
-        return f'k_attention_w8q2<64, 4, {p}, false>'
+        return f'k_attention_w8<64, 4, {p}, false, 2>'
     if hd <= 48 and wide == 2 and q2 and case.n_q >= 2048 and case.n_k >= 64:
         if hd == 40 and pre and m32:
             return 'k_attention_w8q2m'
-        return f'k_attention_w8q2<64, 3, {p}, {"true" if hd <= 40 else "false"}>'
+        return f'k_attention_w8<64, 3, {p}, {"true" if hd <= 40 else "false"}, 2>'
     if hd <= 48:
-        return f'k_attention_w8<64, 3, {p}, {"true" if hd <= 40 else "false"}>' if wide == 2 else old(64, 3)
+        return f'k_attention_w8<64, 3, {p}, {"true" if hd <= 40 else "false"}, 1>' if wide == 2 else old(64, 3)
     if hd <= 64:
-        return f'k_attention_w8<64, 4, {p}, false>' if wide == 2 else old(64, 4)
+        return f'k_attention_w8<64, 4, {p}, false, 1>' if wide == 2 else old(64, 4)
     if hd <= 80:
-        return f'k_attention_w8<96, 5, {p}, false>' if wide == 2 else old(96, 5)
+        return f'k_attention_w8<96, 5, {p}, false, 1>' if wide == 2 else old(96, 5)
     if hd <= 96:
         return 'k_attention<96, 6>'
     if hd <= 128:
         return 'k_attention<128, 8>'
-    return f'k_attention_w8<160, 10, {p}, false>' if wide == 2 else old(160, 10)
+    return f'k_attention_w8<160, 10, {p}, false, 1>' if wide == 2 else old(160, 10)
 
 
 def refused(case: Case, env={}) -> bool:
@@ -156,7 +161,7 @@ def refused(case: Case, env={}) -> bool:
 
 
 def grid_size(case: Case, env={}) -> int:
-    rows = 256 if template_of(expected_kernel(case, env)) in ('k_attention_w8q2', 'k_attention_w8q2m') else 128
+    rows = 256 if family_of(expected_kernel(case, env)) in (('k_attention_w8', 2), ('k_attention_w8q2m', None)) else 128
     return -(-case.n_q // rows) * case.heads * case.B
 
 

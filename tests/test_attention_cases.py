@@ -10,7 +10,7 @@ import torch
 import attention_cases as A
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SCREEN_CAP = 1 << 22     # B * heads * n_q * n_k of a screened case (2048 x 2048 of one head: the smallest w8q2<64, 4> causal case)
+SCREEN_CAP = 1 << 22     # B * heads * n_q * n_k of a screened case (2048 x 2048 of one head: the smallest k_attention_w8<64, 4, *, false, 2> causal case)
 LIVE = [c for c in A.CASES if not A.refused(c)]
 SCREENED = [c for c in LIVE if c.B * c.heads * c.n_q * c.n_k <= SCREEN_CAP]
 
@@ -18,25 +18,20 @@ SCREENED = [c for c in LIVE if c.B * c.heads * c.n_q * c.n_k <= SCREEN_CAP]
 def _dispatcher_text():
     with open(os.path.join(ROOT, 'flexdiffuse_amd', 'csrc', 'attention.hip'), encoding='utf-8') as f:
         src = f.read()
-    return src, src[src.index('extern "C" int fd_attention_f16'):]
+    return src, src[src.index('// Host side: check the descriptor, choose the kernel, launch it.'):]
 
 
 def _launch_targets():
-    '''Every hipLaunchKernelGGL target of fd_attention_f16, with the ATT_W8(DQK, DV, ONES) macro expanded by hand.'''
+    '''Every kernel fd_attention_f16 can launch.  Its one hipLaunchKernelGGL launches what attn_choose returns, and
+    attn_choose returns an entry of the ATTN_BANDS or ATTN_LAZY table or the one kernel it names itself: so the targets
+    are the kernel names between the first table and the end of attn_choose, each spelled in full there.'''
     _, body = _dispatcher_text()
-    body = body.replace('\\\n', ' ')
-    macro = re.search(r'#define ATT_W8\(DQK, DV, ONES\)(.*)', body).group(1)
-    uses = re.findall(r'ATT_W8\((\d+), (\d+), (true|false)\)', body)
-    assert uses, 'ATT_W8 is no longer used: update tests/attention_cases.py'
-    text = '\n'.join(ln for ln in body.split('\n') if not ln.startswith('#define ATT_W8'))
-    for dqk, dv, ones in uses:
-        text += re.sub(r'\bONES\b', ones, re.sub(r'\bDV\b', dv, re.sub(r'\bDQK\b', dqk, macro)))
-    targets = set()
-    for m in re.finditer(r'hipLaunchKernelGGL\(\s*(\(?)', text):
-        rest = text[m.end():]
-        name = rest[:rest.index('>)') + 1] if m.group(1) else rest[:rest.index(',')]
-        targets.add(name.strip())
-    return targets
+    assert body.count('hipLaunchKernelGGL(') == 1 and 'hipLaunchKernelGGL(c.kernel, ' in body
+    assert body.count('attn_choose(') == 2 and 'const AttnChoice c = attn_choose(' in body      # the definition and its one use
+    tables = body[body.index('static const AttnBand ATTN_BANDS[]'):body.index('static int attn_check(')]
+    assert 'static const AttnLazyRow ATTN_LAZY[]' in tables and 'static AttnChoice attn_choose(' in tables
+    code = '\n'.join(ln.split('//')[0] for ln in tables.split('\n'))
+    return set(re.findall(r'\bk_attention\w*(?:<[^<>]*>)?', code))
 
 
 def _reachable():
@@ -56,9 +51,8 @@ def test_restated_dispatcher_names_the_launch_targets_of_the_source():
     reach = _reachable()
     assert set(reach) <= targets, f'names not launched by fd_attention_f16: {sorted(set(reach) - targets)}'
     assert targets <= set(reach), f'launch targets without a case: {sorted(targets - set(reach))}'
-    for name in reach:     # the spelling exists in the source (w8 names: through the macro's own text)
-        spelled = name if not name.startswith('k_attention_w8<') else 'k_attention_w8<DQK, DV, %s, ONES>' % name.split(', ')[2]
-        assert spelled in src, spelled
+    for name in reach:     # the spelling exists in the source
+        assert name in src, name
     for env in A.ENV_SETTINGS:
         (var, _), = env.items()
         assert f'getenv("{var}")' in src
@@ -71,7 +65,7 @@ def test_default_build_reaches_every_default_kernel_prescaled_and_not():
     old = {n for n in _launch_targets() if n.startswith('k_attention<') and n not in ('k_attention<96, 6>', 'k_attention<128, 8>')}
     assert set(default) == _launch_targets() - old
     for name in default:     # `true` and `false` PRE twins both present by the set equality above
-        assert A.template_of(name) in ('k_attention', 'k_attention_w8', 'k_attention_w8q2', 'k_attention_w8q2m')
+        assert A.family_of(name) in (('k_attention', None), ('k_attention_w8', 1), ('k_attention_w8', 2), ('k_attention_w8q2m', None))
     refusals = [c for c in A.CASES if A.refused(c)]
     assert sorted((c.d, c.pre) for c in refusals) == [(88, True), (128, True)]
 
@@ -85,17 +79,17 @@ def test_table_covers_what_it_promises():
     # both sides of each dispatch threshold, on a head dim where the threshold decides the kernel
     k = A.expected_kernel
     pick = lambda **kw: [c for c in LIVE if all(getattr(c, n) == v for n, v in kw.items())]
-    assert {A.template_of(k(c)) for c in pick(n_q=2047, d=40)} == {'k_attention_w8'} and pick(n_q=2047, d=40)
-    assert {A.template_of(k(c)) for c in pick(n_q=2048, n_k=1024, d=40)} == {'k_attention_w8q2', 'k_attention_w8q2m'}
-    assert [k(c) for c in pick(n_q=2048, n_k=63)] == ['k_attention_w8<64, 3, true, true>']
+    assert {A.family_of(k(c)) for c in pick(n_q=2047, d=40)} == {('k_attention_w8', 1)} and pick(n_q=2047, d=40)
+    assert {A.family_of(k(c)) for c in pick(n_q=2048, n_k=1024, d=40)} == {('k_attention_w8', 2), ('k_attention_w8q2m', None)}
+    assert [k(c) for c in pick(n_q=2048, n_k=63)] == ['k_attention_w8<64, 3, true, true, 1>']
     assert 'k_attention_w8q2m' in [k(c) for c in pick(n_q=2048, n_k=64)]
-    assert [k(c) for c in pick(n_q=2048, n_k=1023, d=64)] == ['k_attention_w8<64, 4, true, false>']
-    assert [k(c) for c in pick(n_q=2048, n_k=1024, d=64)] == ['k_attention_w8q2<64, 4, false, false>']
+    assert [k(c) for c in pick(n_q=2048, n_k=1023, d=64)] == ['k_attention_w8<64, 4, true, false, 1>']
+    assert [k(c) for c in pick(n_q=2048, n_k=1024, d=64)] == ['k_attention_w8<64, 4, false, false, 2>']
     assert any(c.causal and c.n_q < c.n_k for c in LIVE) and any(c.causal and c.n_q > c.n_k for c in LIVE)
-    by_template = {}
+    by_template = {}      # per (template, query blocks per wave)
     for c in LIVE:
-        by_template.setdefault(A.template_of(k(c)), []).append(c)
-    assert set(by_template) == {'k_attention', 'k_attention_w8', 'k_attention_w8q2', 'k_attention_w8q2m'}
+        by_template.setdefault(A.family_of(k(c)), []).append(c)
+    assert set(by_template) == {('k_attention', None), ('k_attention_w8', 1), ('k_attention_w8', 2), ('k_attention_w8q2m', None)}
     for t, cases in by_template.items():
         assert {c.layout for c in cases} == set(A.LAYOUTS), t
         assert any(c.scale > 0 for c in cases), t
@@ -171,14 +165,14 @@ def test_check_accepts_fp16_rounded_fp32_and_rejects_every_mutant(screen, case):
 
 def test_every_kernel_name_saw_the_mutants(screen):
     '''Each default kernel name had the size-independent mutants applied, and every mutant was applied somewhere on
-    each template.'''
+    each template and number of query blocks per wave.'''
     applied = {}
     for case in SCREENED:
         applied.setdefault(A.expected_kernel(case), set()).update(screen[case.id][1])
     by_template = {}
     for name, seen in applied.items():
         assert seen >= {'drop_last_key', 'scale_3pct'}, (name, seen)
-        by_template.setdefault(A.template_of(name), set()).update(seen)
+        by_template.setdefault(A.family_of(name), set()).update(seen)
     for t, seen in by_template.items():
         assert seen == set(A.MUTANTS), (t, set(A.MUTANTS) - seen)
 

@@ -1468,7 +1468,7 @@ def test_runner_compose(dev):
 # ---- full-size towers / decoder and the c5 (OpenCLIP ViT-H) shapes ------------------------------
 def test_vit_h_shaped_mini_towers_vs_oracle(dev):
     '''BASELINE configs[4]'s guide towers in miniature: OpenCLIP-style erf-GELU MLPs, vision
-    head dim 80 (the non-prescaled k_attention_w8<96,5> path), text head dim 64, 2 layers each,
+    head dim 80 (the non-prescaled k_attention_w8<96,5,false,false,1> path), text head dim 64, 2 layers each,
     against oracle.clip_ref on fp16-exact seeded weights.  Reference call sites:
     encode/clip.py:47-65 (prompt), :86-100 (image).'''
     from flexdiffuse_amd import weights as W

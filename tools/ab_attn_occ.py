@@ -1,5 +1,5 @@
 '''Self-attention at the level-0 shape (B 16, N 4096, 8 heads x 40) across library variants
-(FD_LIB_PATH): occupancy 8 / 6 / 4 waves per SIMD of k_attention_w8<64,3>.'''
+(FD_LIB_PATH): occupancy 8 / 6 / 4 waves per SIMD of k_attention_w8<64,3,*,*,1>.'''
 import sys, os, subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,5 @@
 '''Self-attention at head dim 64 (SD2.1 at 768x768: 16 x 5 heads x 9216 x 9216 at the top level, 10 heads x 2304 below; Q pre-scaled): two query blocks per wave
-(k_attention_w8q2<64,4>, FD_ATTN_Q2_64=1, default) against one (k_attention_w8<64,4>, FD_ATTN_Q2_64=0); variant libraries tools/_variants/libfd_q264_*.so
+(k_attention_w8<64,4,*,false,2>, FD_ATTN_Q2_64=1, default) against one (k_attention_w8<64,4,*,false,1>, FD_ATTN_Q2_64=0); variant libraries tools/_variants/libfd_q264_*.so
 are further arms.  One process per arm, interleaved.
     python tools/ab_attn_q2_64.py'''
 import sys, os, subprocess

@@ -1,6 +1,6 @@
 // Would v_mfma_f32_32x32x16_f16 pay in the head-dim-40 self-attention tile loop?  
 // One iteration = the MFMA + VALU instruction mix of ONE 64-key K/V tile for 32 queries of one wave of
-// k_attention_w8q2 (registers only: no LDS, no loads; operands are random fp16 so the power / clock effect of
+// the two-block k_attention_w8 (registers only: no LDS, no loads; operands are random fp16 so the power / clock effect of
 // real toggle rates is included), 16 waves per CU (4 per SIMD) like the product kernel at 128 VGPRs:
 //   MODE 0  product form:  S^T = K Q^T as 16 x v_mfma_16x16x32 (2 query blocks x 4 key blocks x 2 k-steps, head dim 40
 //           padded to 64), 32 v_exp_f32 + 16 v_cvt_pk + 16 v_max3 per lane, PV as 12 x v_mfma_16x16x32 (3 d-tiles of 16)

@@ -12,7 +12,7 @@ NOTES = {  # kernel -> (description, algorithmic bytes per launch)
     'void k_gemm_f16_dmap<256, 256, false, 4, false, 4, 6>': ('level-0 GEGLU 65536x2560x320 with the LayerNorm fold, 256x256 tile, packed-fp32 GELU epilogue', 65536 * 320 * 2 + 65536 * 1280 * 2),
     'void k_xattn<40>': ('fused q projection + cross-attention, 8 heads x 40, 16x4096 rows, 77 keys', 2 * 65536 * 320 * 2),
     'void k_xattn<80>': ('fused q projection + cross-attention, 8 heads x 80 (32x32 level), 16x1024 rows, 77 keys', 2 * 16384 * 640 * 2),
-    'void k_attention_w8q2<64, 3, true, true>': ('the cross-attention launch k_xattn<40> replaces (16x4096 queries, 77 keys)', 2 * 65536 * 320 * 2),
+    'void k_attention_w8<64, 3, true, true, 2>': ('the cross-attention launch k_xattn<40> replaces (16x4096 queries, 77 keys)', 2 * 65536 * 320 * 2),
     'void k_gemm_f16_dma<256, 160, true, 8, false, 2, 2, 0>': ('8x8-level conv3x3 M 1024 N 1280 K 11520, split-K 8 partial pass (fp32 slabs)', 1024 * 1280 * 2 * 2 + 1280 * 11520 * 2),
     'k_splitk_finish': ('its finish kernel (8 fp32 slabs -> fp16)', 0),
     'void k_gemm_f16_dma<288, 160, true, 6, false, 2, 2, 1>': ('768x768 level-0 conv3x3 8x96x96x320->320 (M 73728, N 320, K 2880) on the 288x160 tile (12 waves)', 2 * (73728 * 320 * 2) + 320 * 2880 * 2),
